@@ -9,12 +9,16 @@ torch.distributed.run, one process per GPU) the objects are sharded: --scaling w
 `--reviews` objects, --scaling strong splits `--reviews` objects over the ranks (configs[3]: --reviews 10000000); the
 per-shard violation bitmaps / counts are exchanged with one RCCL all-gather inside every step.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps, writes the last step's outputs
+(--dump-outputs DIR) and prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the
+workload (`config`) and the ingest figures of the table it built (`end_to_end`).  --full adds every leg below (the line printed
+by earlier rounds); --lean adds the roofline figures alone:
   roofline      dominant kernel: algorithmic bytes per launch / average launch duration (HIP events) vs 8 TB/s HBM
   end_to_end    the PCIe-inclusive leg: host parse + HandleReview + flatten + H2D of the same objects (never `value`)
   cpu_baseline  the independent compiled restatement of the reference's loop (oracle/indep_check.cpp) on 1 thread and on all host cores
   parity_sample / parity_compiled_independent   the device bitmaps of the timed table against that checker, every object, bit for bit
   parity_python_oracle   ... and against the pure-Python oracle (no code shared with the product either)
+  other_configs configs[1], configs[4] resident + streaming and configs[3]'s N = 1 point, each with its own parity leg
 """
 import argparse
 import json
@@ -26,6 +30,96 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 48 << 20    # --dump-outputs: bytes of the sampled per-object arrays at most (the per-constraint totals come on top)
+DUMP_OBJECTS = 65536     # ... and objects in that sample at most
+DUMP_SEED = 20240601     # the sample's objects: the same for every run of the same arguments
+
+
+def read_device(lib, ptr, nbytes, emu):
+    """`nbytes` at a device address the engine handed out, as uint8 on the host.  hipMemcpy is looked up through the engine's
+    library handle, i.e. in the HIP runtime the engine itself runs on; the CPU emulation's 'device' memory is host memory."""
+    import ctypes as C
+    import numpy as np
+    buf = np.empty(nbytes, np.uint8)
+    if nbytes == 0:
+        return buf
+    if emu:
+        C.memmove(buf.ctypes.data, ptr, nbytes)
+        return buf
+    fn = lib.hipMemcpy
+    fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], C.c_int
+    rc = fn(buf.ctypes.data, ptr, nbytes, 2)   # hipMemcpyDeviceToHost
+    if rc != 0:
+        raise RuntimeError("hipMemcpy of %d bytes from the engine's result buffers failed: hipError %d" % (nbytes, rc))
+    return buf
+
+
+def last_step_outputs(last, table, sweep, lib, emu):
+    """What the timed path's last step computed, read from where its collecting call left it on the device (the caller of the
+    timed path gets device pointers: GK_EVAL_NO_DOWNLOAD) -> dict with
+      ids       constraint ids in bitmap-row order
+      shards    [(first object, objects, violation bitmap [rows][words], autoreject bitmap [rows][words] or None)]
+      counts    violating objects per row, over every object;  err_pairs: autoreject pairs per row, over every object
+    Single process: the table's bitmaps and counts (d_viol / d_err / d_counts).  Sharded: the gathered [bitmap | counts | tail]
+    slots of every rank (d_gathered; autoreject bitmaps are not exchanged) and the global totals.  A constraint set of several
+    plan groups has no one device buffer: the same step is then taken once more with a download (the device's answer alone)."""
+    import numpy as np
+    if sweep.dist is not None:
+        if last.gathered is None:
+            if last.d_gathered:
+                last.gathered = read_device(lib, last.d_gathered, last.world * last.slot_bytes, emu).reshape(last.world, last.slot_bytes)
+            else:
+                last = sweep.sweep(1, download=True)       # (collective: every rank takes this branch alike)
+        offsets = np.concatenate([[0], np.cumsum(last.shard_reviews.astype(np.int64))])
+        shards = [(int(offsets[r]), int(last.shard_reviews[r]), bm, None) for r, bm in enumerate(last.bitmaps())]
+        return {"ids": last.constraint_ids, "shards": shards, "counts": last.totals.astype(np.float64), "err_pairs": last.err_totals.astype(np.float64)}
+    nc, nt, n = int(last.n_constraints), int(last.n_tiles), int(last.n_reviews)
+    if last.d_viol and last.d_err and last.d_counts:
+        viol = read_device(lib, last.d_viol, nc * nt * 8, emu).view(np.uint64).reshape(nc, nt)
+        err = read_device(lib, last.d_err, nc * nt * 8, emu).view(np.uint64).reshape(nc, nt)
+        counts = read_device(lib, last.d_counts, nc * 4, emu).view(np.uint32)
+    else:
+        table.launch()
+        ev = table.eval(download=True, collect_only=True, host_eval=False)
+        viol, err, counts = ev.viol, ev.err, ev.counts
+    words = (n + 63) // 64
+    valid = np.full(words, np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64)
+    if n % 64:
+        valid[-1] = np.uint64((1 << (n % 64)) - 1)
+    err_pairs = np.array([int(np.unpackbits((err[r, :words] & valid).view(np.uint8)).sum()) for r in range(nc)], np.float64)
+    return {"ids": last.constraint_ids, "shards": [(0, n, viol, err)], "counts": counts.astype(np.float64), "err_pairs": err_pairs}
+
+
+def write_outputs(dirpath, got, order, n_total):
+    """--dump-outputs: the last step's outputs as DIR/<name>.npy, rows in the order the constraints were loaded (`order`: ids)
+      violations.npy                       float32 [constraints][sample]: 1 = the constraint applies to the object and is violated
+      autoreject.npy                       float32, same shape: Matcher.Match failed (autoreject); single process only
+      sample_objects.npy                   float64 [sample]: the objects of the sample (indices into the synthetic stream)
+      violating_objects_per_constraint.npy float64 [constraints], over every object
+      autoreject_pairs_per_constraint.npy  float64 [constraints], over every object
+    The sample is every object when they fit into DUMP_BYTES, else a fixed seeded sample (DUMP_SEED)."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    row_of = {int(cid): i for i, cid in enumerate(got["ids"])}
+    rows = np.array([row_of[int(cid)] for cid in order], np.int64)
+    with_err = all(s[3] is not None for s in got["shards"])
+    per_object = 4 * len(rows) * (2 if with_err else 1)
+    m = int(min(n_total, DUMP_OBJECTS, max(1, DUMP_BYTES // max(1, per_object))))
+    idx = np.arange(n_total, dtype=np.int64) if m >= n_total else np.sort(np.random.default_rng(DUMP_SEED).choice(n_total, m, replace=False))
+
+    def bits(k):
+        out = np.zeros((len(rows), len(idx)), np.float32)
+        for first, n, *bms in got["shards"]:
+            sel = (idx >= first) & (idx < first + n)
+            j = idx[sel] - first
+            out[:, sel] = ((bms[k][rows][:, j >> 6] >> (j & 63).astype(np.uint64)) & np.uint64(1)).astype(np.float32)
+        return out
+    arrays = {"violations": bits(0), "sample_objects": idx.astype(np.float64),
+              "violating_objects_per_constraint": got["counts"][rows], "autoreject_pairs_per_constraint": got["err_pairs"][rows]}
+    if with_err:
+        arrays["autoreject"] = bits(1)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def indep_leg(templates, constraints, batch, ev, ids=None, budget_s=8.0, n=None):
@@ -624,6 +718,10 @@ def main():
                     help="1: 30 PSP x Pods (configs[1]); 2: 50 constraints x mixed objects (configs[2]); 4: the 200-template policy corpus x mixed objects (configs[4]'s policy set)")
     ap.add_argument("--reviews", type=int, default=None, help="objects per GPU (weak) / in total (strong); default 1000000 (config 2), 100000 (config 1)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
+    ap.add_argument("--full", action="store_true", help="everything else the benchmark measures and checks: the roofline and per-kernel figures, the RESULT "
+                    "totals, the CPU baseline, the parity legs and (the default workload) other_configs -- without it a run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(float32 / float64, %d MiB at most; see write_outputs)" % (DUMP_BYTES >> 20))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--lean", action="store_true", help="tuning runs: the timed sweep and the roofline figures only (no RESULT totals, no CPU / oracle legs)")
     ap.add_argument("--streaming", action="store_true", help="configs[4] as a STREAM: batches of --batch reviews through ingest -> H2D -> launch -> D2H, "
@@ -643,6 +741,10 @@ def main():
     ap.add_argument("--test-hostemu", action="store_true", help="TEST ONLY (tests/test_bench_dist.py): the CPU emulation build of the engine and gloo instead of an MI355X "
                     "and RCCL, to exercise this file's sharded path in the GPU-less build container; the line says so (`emulated`) and is not a measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.streaming:
+        ap.error("--dump-outputs writes the outputs of the resident sweep; --streaming has none to keep")
     # ---- ranks.  The driver starts N > 1 as `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` (WORLD_SIZE set);
     # a bare `python bench.py --gpus N` starts its own N ranks the same way.  Either way the line is printed only if the job really
     # has N ranks: a world size that differs from --gpus is an error (exit 2), never a silent N = 1 line.
@@ -665,7 +767,10 @@ def main():
     if env_world != args.gpus:
         sys.stderr.write("bench.py: --gpus %d but the launcher started %d rank(s) (WORLD_SIZE): refusing to print a line for another job size\n" % (args.gpus, env_world))
         sys.exit(2)
-    want_others = args.config is None and not args.no_other_configs and not args.lean and not args.streaming and args.scaling == "weak" and args.reviews is None
+    # --full: every leg; --lean: the roofline figures alone (`measure`); a plain run: the timed steps
+    measure = args.full or args.lean
+    checks = args.full and not args.lean
+    want_others = checks and args.config is None and not args.no_other_configs and not args.streaming and args.scaling == "weak" and args.reviews is None
     if args.config is None:
         args.config = 2
     if args.reviews is None:
@@ -763,7 +868,7 @@ def main():
     table = drv.engine.create_table_native(batch.reviews, n_local, keep_docs=False, resident=True, keep_text=True, pruned=not getattr(args, "no_prune", False))   # (text kept by `batch`: RESULT totals below)
     st = table.stats()
     st_again = None
-    if not args.lean and n_local <= 2_000_000:   # the same batch once more: what ingest costs once the host threads' caches, the staging pool and the path tables are warm
+    if checks and n_local <= 2_000_000:   # the same batch once more: what ingest costs once the host threads' caches, the staging pool and the path tables are warm
         again = drv.engine.create_table_native(batch.reviews, n_local, keep_docs=False, resident=True, pruned=not getattr(args, "no_prune", False))
         st_again = again.stats()
         again.free()
@@ -793,21 +898,28 @@ def main():
         step(args.warmup)
     barrier()
     t0 = time.perf_counter()
-    step(args.steps)                       # exactly `steps` passes (+ exchanges when sharded) in the timed region
+    last = step(args.steps)                # exactly `steps` passes (+ exchanges when sharded) in the timed region
     barrier()
     dt = time.perf_counter() - t0
-    sharded = sweep.sweep(1, download=False) if dist is not None else None
-    res = local(min(args.steps, 20))       # launch-to-launch average of the whole step (and the per-launch byte accounting)
-    # The dominant kernel's own duration by HIP events on its stream, two ways: (a) ONE event pair around `steps` consecutive launches
-    # of that kernel alone (GK_EVAL_KERNEL_ONLY: no totals kernel in between) -- the average includes the gap between two launches;
-    # (b) an event pair per launch (GK_EVAL_TIME_EACH) -- every bracket includes the dispatch of the kernel behind an event record,
-    # 3-4 us on a 65 us kernel (round 5: 68.2 us by (b), 64.3 us by rocprofv3's kernel trace of the same build).  `roofline` uses (a).
-    b2b = local(min(args.steps, 20), kernel_only=True) if dist is None else None
-    final = local(1, download=True)
-    counts = final.counts
-    # isolated kernel duration: a second, untimed pass with one HIP event pair per launch (the timed region above
-    # brackets all launches with one pair, i.e. its average includes the gaps between consecutive launches)
-    iso = local(min(args.steps, 20), time_each=True)
+    if args.dump_outputs:                  # (before any further launch: the device buffers hold the last timed step's answer)
+        got = last_step_outputs(last, table, sweep, drv.engine.lib, emu)
+        if rank == 0:
+            write_outputs(args.dump_outputs, got, batch_constraint_ids, total_reviews)
+        got = None
+    sharded = res = b2b = final = iso = None
+    if measure:
+        sharded = sweep.sweep(1, download=False) if dist is not None else None
+        res = local(min(args.steps, 20))       # launch-to-launch average of the whole step (and the per-launch byte accounting)
+        # The dominant kernel's own duration by HIP events on its stream, two ways: (a) ONE event pair around `steps` consecutive launches
+        # of that kernel alone (GK_EVAL_KERNEL_ONLY: no totals kernel in between) -- the average includes the gap between two launches;
+        # (b) an event pair per launch (GK_EVAL_TIME_EACH) -- every bracket includes the dispatch of the kernel behind an event record,
+        # 3-4 us on a 65 us kernel (round 5: 68.2 us by (b), 64.3 us by rocprofv3's kernel trace of the same build).  `roofline` uses (a).
+        b2b = local(min(args.steps, 20), kernel_only=True) if dist is None else None
+        final = local(1, download=True)
+        counts = final.counts
+        # isolated kernel duration: a second, untimed pass with one HIP event pair per launch (the timed region above
+        # brackets all launches with one pair, i.e. its average includes the gaps between consecutive launches)
+        iso = local(min(args.steps, 20), time_each=True)
     if dist is not None:
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -816,11 +928,6 @@ def main():
     if rank == 0:
         nc = len(constraints)
         evals = float(nc) * total_reviews * args.steps
-        # average duration of the dominant kernel alone: back to back under one event pair when there is one plan group, else per-launch events
-        kernel_b2b_ms = float(b2b.fast_kernel_ms) if (b2b is not None and len(constraints) <= 64 and b2b.fast_kernel_ms > 0) else None
-        kernel_s = (kernel_b2b_ms if kernel_b2b_ms is not None else iso.fast_kernel_ms) / 1e3
-        achieved = res.algo_bytes / kernel_s / 1e9 if kernel_s > 0 else 0.0
-        full_table_bytes = int(res.n_rows) * 16 + n_local * 4   # what a kernel streaming every row would read
         cfg_name = ("configs[1]: 30 gatekeeper PSP constraints (5 in-tree PSP templates x 6 parameterisations) x %d synthetic Pod "
                     "AdmissionReviews" if args.config == 1 else
                     "configs[4] policy set: 200 ConstraintTemplates + 200 constraints (required labels/allowedRegex, allowed repos, banned image tags, "
@@ -836,37 +943,10 @@ def main():
             # ranks of the engine's own communicator, read back from RCCL (ncclCommCount) after gk_comm_init; null: one process, no exchange step
             "rccl_ranks": rccl_ranks,
             "config": {"workload": cfg_name, "constraints": nc, "reviews_total": total_reviews, "reviews_rank0": n_local,
-                       "rows_rank0": int(res.n_rows), "rows_read_rank0": int(res.n_rows_read), "table_bytes_rank0": int(st["device_bytes"]),
-                       "timed_region_s": dt,
+                       "rows_rank0": int(st["n_rows"]), "table_bytes_rank0": int(st["device_bytes"]), "timed_region_s": dt,
                        "parallelism": ("objects block-sharded across %d GPUs; per sweep ONE in-place ncclAllGather of [violation bitmaps | counts | fail-closed counts] "
                                        "issued by the engine on the kernel's stream (global totals = sums over the gathered slot tails); four enqueues "
-                                       "per pass, no host round trip" % world) if dist is not None else "1 GPU",
-                       "global_violating_pairs": int(sharded.totals.sum()) if sharded is not None else int(counts.sum()),
-                       "violating_pairs_rank0": int(counts.sum()), "reviews_beyond_limits_rank0": len(final.too_big_reviews()),
-                       # reviews beyond the DEVICE's limits that the engine's exact host evaluator answered instead of refusing them
-                       "reviews_evaluated_on_host_rank0": len(getattr(final, "host_evaluated", []))},
-            # N > 1: what the exchange step costs next to the local sweep (rank 0's figures of one collecting sweep behind the timed region:
-            # HIP events around the all-gather alone; the timed passes are enqueue-only and carry no events).  `ms_per_step` against
-            # sweep_ms_local + exchange_ms says whether the overlapped exchange (GK_SHARD_OVERLAP=1, opt-in) hid it.
-            "exchange": None if sharded is None else {
-                "exchange_bytes_per_rank": sharded.exchange_bytes_inbound, "exchange_ms": sharded.exchange_ms, "sweep_ms_local": float(sharded.fast_kernel_ms),
-                "overlap_enabled": sharded.exchange_overlapped, "slot_bytes": int(sharded.slot_bytes),
-                "exchange_GBps_inbound": sharded.exchange_bytes_inbound / (sharded.exchange_ms * 1e6) if sharded.exchange_ms > 0 else None,
-                "hidden_by_overlap": (dt / args.steps * 1e3) < 0.75 * (float(sharded.fast_kernel_ms) + sharded.exchange_ms) if sharded.exchange_ms > 0 else None,
-                "bound": ("exchange" if sharded.exchange_ms > float(sharded.fast_kernel_ms) else "sweep") if sharded.exchange_ms > 0 else None},
-            # (the plan-specialised build -- what rocprofv3 shows for this workload; GK_NO_JIT=1 runs the generic bytecode build instead)
-            "roofline": {"bound": "hbm", "kernel": "gk_eval_tiles_256" if os.environ.get("GK_NO_JIT") else "gk_jit_tiles", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": None, "algo_bytes_per_launch": int(res.algo_bytes),
-                         "avg_kernel_ms": kernel_s * 1e3, "launches_timed": int((b2b if kernel_b2b_ms is not None else iso).n_launches),
-                         "clock": ("HIP events on the launch stream: one pair around %d consecutive launches of the kernel alone (GK_EVAL_KERNEL_ONLY)" % int(b2b.n_launches)) if kernel_b2b_ms is not None
-                                  else "HIP events on the launch stream: one pair per launch (GK_EVAL_TIME_EACH)",
-                         "avg_kernel_ms_event_pair_per_launch": iso.fast_kernel_ms,
-                         # (one event pair around all launches of a view; the plan groups of a >64-formula constraint set share
-                         #  the stream, so the figure is only meaningful for a single group)
-                         "avg_launch_ms_back_to_back": res.fast_kernel_ms if nc <= 64 else None, "lds_bytes_per_tile": int(res.lds_bytes), "kernel_text_hash": "%016x" % int(res.kernel_text_hash),
-                         "full_table_bytes": full_table_bytes,
-                         "full_table_GBps": full_table_bytes / kernel_s / 1e9 if kernel_s > 0 else None,
-                         "kernel_only_evals_per_s": nc * n_local / kernel_s if kernel_s > 0 else None},
+                                       "per pass, no host round trip" % world) if dist is not None else "1 GPU"},
             "end_to_end": {"what": "rank 0: JSON text -> parse -> HandleReview -> flatten -> row groups -> HBM for the %d objects of its shard "
                                    "(gk_table_create), then one sweep" % n_local,
                            "flatten_s": st["flatten_s"], "h2d_s": st["upload_s"], "sweep_s": dt / args.steps, "host_threads": st["host_threads"],
@@ -878,7 +958,41 @@ def main():
                                                                                         "json_MBps": st_again["json_bytes"] / st_again["flatten_s"] / 1e6 if st_again["flatten_s"] > 0 else None},
                            "generate_s": t_gen},
         }
-        if args.config == 2 and n_local == 1000000 and world == 1 and kernel_s > 0 and not os.environ.get("GK_DICT_MATCH"):
+        if measure:
+            # average duration of the dominant kernel alone: back to back under one event pair when there is one plan group, else per-launch events
+            kernel_b2b_ms = float(b2b.fast_kernel_ms) if (b2b is not None and len(constraints) <= 64 and b2b.fast_kernel_ms > 0) else None
+            kernel_s = (kernel_b2b_ms if kernel_b2b_ms is not None else iso.fast_kernel_ms) / 1e3
+            achieved = res.algo_bytes / kernel_s / 1e9 if kernel_s > 0 else 0.0
+            full_table_bytes = int(res.n_rows) * 16 + n_local * 4   # what a kernel streaming every row would read
+            out["config"].update({
+                "rows_rank0": int(res.n_rows), "rows_read_rank0": int(res.n_rows_read),
+                "global_violating_pairs": int(sharded.totals.sum()) if sharded is not None else int(counts.sum()),
+                "violating_pairs_rank0": int(counts.sum()), "reviews_beyond_limits_rank0": len(final.too_big_reviews()),
+                # reviews beyond the DEVICE's limits that the engine's exact host evaluator answered instead of refusing them
+                "reviews_evaluated_on_host_rank0": len(getattr(final, "host_evaluated", []))})
+            # N > 1: what the exchange step costs next to the local sweep (rank 0's figures of one collecting sweep behind the timed region:
+            # HIP events around the all-gather alone; the timed passes are enqueue-only and carry no events).  `ms_per_step` against
+            # sweep_ms_local + exchange_ms says whether the overlapped exchange (GK_SHARD_OVERLAP=1, opt-in) hid it.
+            out["exchange"] = None if sharded is None else {
+                "exchange_bytes_per_rank": sharded.exchange_bytes_inbound, "exchange_ms": sharded.exchange_ms, "sweep_ms_local": float(sharded.fast_kernel_ms),
+                "overlap_enabled": sharded.exchange_overlapped, "slot_bytes": int(sharded.slot_bytes),
+                "exchange_GBps_inbound": sharded.exchange_bytes_inbound / (sharded.exchange_ms * 1e6) if sharded.exchange_ms > 0 else None,
+                "hidden_by_overlap": (dt / args.steps * 1e3) < 0.75 * (float(sharded.fast_kernel_ms) + sharded.exchange_ms) if sharded.exchange_ms > 0 else None,
+                "bound": ("exchange" if sharded.exchange_ms > float(sharded.fast_kernel_ms) else "sweep") if sharded.exchange_ms > 0 else None}
+            # (the plan-specialised build -- what rocprofv3 shows for this workload; GK_NO_JIT=1 runs the generic bytecode build instead)
+            out["roofline"] = {"bound": "hbm", "kernel": "gk_eval_tiles_256" if os.environ.get("GK_NO_JIT") else "gk_jit_tiles", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": None, "algo_bytes_per_launch": int(res.algo_bytes),
+                               "avg_kernel_ms": kernel_s * 1e3, "launches_timed": int((b2b if kernel_b2b_ms is not None else iso).n_launches),
+                               "clock": ("HIP events on the launch stream: one pair around %d consecutive launches of the kernel alone (GK_EVAL_KERNEL_ONLY)" % int(b2b.n_launches)) if kernel_b2b_ms is not None
+                                        else "HIP events on the launch stream: one pair per launch (GK_EVAL_TIME_EACH)",
+                               "avg_kernel_ms_event_pair_per_launch": iso.fast_kernel_ms,
+                               # (one event pair around all launches of a view; the plan groups of a >64-formula constraint set share
+                               #  the stream, so the figure is only meaningful for a single group)
+                               "avg_launch_ms_back_to_back": res.fast_kernel_ms if nc <= 64 else None, "lds_bytes_per_tile": int(res.lds_bytes), "kernel_text_hash": "%016x" % int(res.kernel_text_hash),
+                               "full_table_bytes": full_table_bytes,
+                               "full_table_GBps": full_table_bytes / kernel_s / 1e9 if kernel_s > 0 else None,
+                               "kernel_only_evals_per_s": nc * n_local / kernel_s if kernel_s > 0 else None}
+        if measure and args.config == 2 and n_local == 1000000 and world == 1 and kernel_s > 0 and not os.environ.get("GK_DICT_MATCH"):
             # Round 5 moved the match layer's five string facts per review (5 rows + 5 string headers = 160 of ~380 bytes) into ONE
             # dictionary row: the sweep streams 234 MB where rounds 1-4 streamed 379 MB -- `frac` is priced on what
             # is streamed NOW, so a launch that got a third faster shows a LOWER fraction.  For the comparison with earlier rounds:
@@ -886,52 +1000,53 @@ def main():
                                                 "what": "the same launch time priced at the bytes the round-4 table layout streamed for this workload (GK_DICT_MATCH=0 builds that layout: 0.1136 ms = 0.417 on the box that ran this layout in 0.0763 ms, profiles/r05_variants_r_match_dictionary.log)"}
         if emu:
             out["emulated"] = True
-        # HBM traffic of the dominant kernel from the committed rocprofv3 PMC passes of this same command (bench.py
-        # cannot run a profiler around itself); only reported when the profiled workload is the one just timed
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_latest.json")))
-            # (... and the profiled build streamed the bytes this one does: a PMC figure of an earlier table layout says nothing)
-            same_bytes = pmc.get("algo_bytes_per_launch") is None or abs(pmc["algo_bytes_per_launch"] - int(res.algo_bytes)) <= 0.02 * int(res.algo_bytes)
-            # (... and ran the kernel text this run timed: the passes are stamped with the hash bench.py printed under them -- a PMC
-            #  figure measured on another kernel or table layout can never ride this line)
-            same_kernel = pmc.get("kernel_text_hash") == "%016x" % int(res.kernel_text_hash)
-            if pmc.get("config") == args.config and pmc.get("reviews") == n_local and world == 1:
-                if same_bytes and same_kernel:
-                    out["roofline"]["traffic"] = pmc["hbm_bytes_per_launch"]
-                    out["roofline"]["traffic_source"] = pmc["source"]
-                    # The SECOND roof.  Round 6 cut the bytes a sweep streams by 45 % (element carriers, the review facts row) and the
-                    # kernel's time by 17 %: `frac` -- bytes over time against the HBM peak -- FELL, although nothing about the memory
-                    # system got worse.  What binds the kernel is instruction issue at the occupancy its LDS footprint allows; the
-                    # SQ counters of the same PMC passes say how close to THAT roof it runs: wave64 VALU instructions per launch
-                    # against what the device's SIMDs can issue in the kernel's duration (a wave64 VALU instruction occupies a
-                    # SIMD-32 for two cycles: 256 CUs x 4 SIMDs x 2.4 GHz / 2), and the share of wave cycles with an instruction in flight.
-                    sq = pmc.get("sq") or {}
-                    if sq.get("SQ_INSTS_VALU") and kernel_s > 0:
-                        peak_valu = 256 * 4 * 2.4e9 / 2.0
-                        out["roofline"]["issue"] = {
-                            "valu_wave_insts_per_launch": sq.get("SQ_INSTS_VALU"), "salu_wave_insts_per_launch": sq.get("SQ_INSTS_SALU"), "lds_wave_insts_per_launch": sq.get("SQ_INSTS_LDS"),
-                            "valu_issue_frac": sq["SQ_INSTS_VALU"] / kernel_s / peak_valu, "peak_valu_wave_insts_per_s": peak_valu,
-                            "waves_waiting_share": (sq.get("SQ_WAIT_ANY") / sq["SQ_WAVE_CYCLES"]) if sq.get("SQ_WAVE_CYCLES") else None,
-                            "waves_issuing_share": (sq.get("SQ_ACTIVE_INST_ANY") / sq["SQ_WAVE_CYCLES"]) if sq.get("SQ_WAVE_CYCLES") else None,
-                            "what": "rocprofv3 --pmc SQ_* of the same command and kernel text (profiles/pmc_latest.json); valu_issue_frac = VALU wave instructions / (kernel time x 256 CUs x 4 SIMD-32 x 2.4 GHz / 2 cycles per wave64 instruction)"}
-                else:
-                    out["roofline"]["traffic_dropped"] = ("profiles/pmc_latest.json was measured on kernel text %s streaming %s bytes per launch; this run timed kernel text %016x "
-                                                          "streaming %d: the stale figure is not reported" % (pmc.get("kernel_text_hash"), pmc.get("algo_bytes_per_launch"),
-                                                                                                             int(res.kernel_text_hash), int(res.algo_bytes)))
-        except (OSError, ValueError):
-            pass
-        # the audit's RESULT totals (pkg/audit/manager.go:893-904: totalViolationsPerConstraint counts types.Results, several per
-        # violating pair) of the MEASURED table.  Round 3: the DEVICE decides, per violating pair, whether the template can yield
-        # more than one result for the review (the totals plans: Template::compile_multi); a pair it does not flag counts one
-        # result unrendered, only the flagged ones are parsed from the batch's JSON text and rendered on the host workers.
-        # Checked here against the host pass over EVERY violating pair (GK_TOTALS_RENDER_ALL=1, the round-2 path).
-        try:
-            if args.lean:
-                raise RuntimeError("skipped (--lean)")
-            out["audit_result_totals"] = totals_leg(table)
-        except Exception as ex:   # noqa: BLE001
-            out["audit_result_totals"] = {"error": "%s: %s" % (type(ex).__name__, ex)}
-        if not args.no_cpu_baseline and not args.lean and world == 1:   # (the checkers and the CPU baseline: N = 1 only -- at N > 1 the other ranks would wait ~2 min for rank 0)
+        if measure:
+            # HBM traffic of the dominant kernel from the committed rocprofv3 PMC passes of this same command (bench.py
+            # cannot run a profiler around itself); only reported when the profiled workload is the one just timed
+            try:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_latest.json")))
+                # (... and the profiled build streamed the bytes this one does: a PMC figure of an earlier table layout says nothing)
+                same_bytes = pmc.get("algo_bytes_per_launch") is None or abs(pmc["algo_bytes_per_launch"] - int(res.algo_bytes)) <= 0.02 * int(res.algo_bytes)
+                # (... and ran the kernel text this run timed: the passes are stamped with the hash bench.py printed under them -- a PMC
+                #  figure measured on another kernel or table layout can never ride this line)
+                same_kernel = pmc.get("kernel_text_hash") == "%016x" % int(res.kernel_text_hash)
+                if pmc.get("config") == args.config and pmc.get("reviews") == n_local and world == 1:
+                    if same_bytes and same_kernel:
+                        out["roofline"]["traffic"] = pmc["hbm_bytes_per_launch"]
+                        out["roofline"]["traffic_source"] = pmc["source"]
+                        # The SECOND roof.  Round 6 cut the bytes a sweep streams by 45 % (element carriers, the review facts row) and the
+                        # kernel's time by 17 %: `frac` -- bytes over time against the HBM peak -- FELL, although nothing about the memory
+                        # system got worse.  What binds the kernel is instruction issue at the occupancy its LDS footprint allows; the
+                        # SQ counters of the same PMC passes say how close to THAT roof it runs: wave64 VALU instructions per launch
+                        # against what the device's SIMDs can issue in the kernel's duration (a wave64 VALU instruction occupies a
+                        # SIMD-32 for two cycles: 256 CUs x 4 SIMDs x 2.4 GHz / 2), and the share of wave cycles with an instruction in flight.
+                        sq = pmc.get("sq") or {}
+                        if sq.get("SQ_INSTS_VALU") and kernel_s > 0:
+                            peak_valu = 256 * 4 * 2.4e9 / 2.0
+                            out["roofline"]["issue"] = {
+                                "valu_wave_insts_per_launch": sq.get("SQ_INSTS_VALU"), "salu_wave_insts_per_launch": sq.get("SQ_INSTS_SALU"), "lds_wave_insts_per_launch": sq.get("SQ_INSTS_LDS"),
+                                "valu_issue_frac": sq["SQ_INSTS_VALU"] / kernel_s / peak_valu, "peak_valu_wave_insts_per_s": peak_valu,
+                                "waves_waiting_share": (sq.get("SQ_WAIT_ANY") / sq["SQ_WAVE_CYCLES"]) if sq.get("SQ_WAVE_CYCLES") else None,
+                                "waves_issuing_share": (sq.get("SQ_ACTIVE_INST_ANY") / sq["SQ_WAVE_CYCLES"]) if sq.get("SQ_WAVE_CYCLES") else None,
+                                "what": "rocprofv3 --pmc SQ_* of the same command and kernel text (profiles/pmc_latest.json); valu_issue_frac = VALU wave instructions / (kernel time x 256 CUs x 4 SIMD-32 x 2.4 GHz / 2 cycles per wave64 instruction)"}
+                    else:
+                        out["roofline"]["traffic_dropped"] = ("profiles/pmc_latest.json was measured on kernel text %s streaming %s bytes per launch; this run timed kernel text %016x "
+                                                              "streaming %d: the stale figure is not reported" % (pmc.get("kernel_text_hash"), pmc.get("algo_bytes_per_launch"),
+                                                                                                                 int(res.kernel_text_hash), int(res.algo_bytes)))
+            except (OSError, ValueError):
+                pass
+            # the audit's RESULT totals (pkg/audit/manager.go:893-904: totalViolationsPerConstraint counts types.Results, several per
+            # violating pair) of the MEASURED table.  Round 3: the DEVICE decides, per violating pair, whether the template can yield
+            # more than one result for the review (the totals plans: Template::compile_multi); a pair it does not flag counts one
+            # result unrendered, only the flagged ones are parsed from the batch's JSON text and rendered on the host workers.
+            # Checked here against the host pass over EVERY violating pair (GK_TOTALS_RENDER_ALL=1, the round-2 path).
+            try:
+                if not checks:
+                    raise RuntimeError("skipped (--lean)")
+                out["audit_result_totals"] = totals_leg(table)
+            except Exception as ex:   # noqa: BLE001
+                out["audit_result_totals"] = {"error": "%s: %s" % (type(ex).__name__, ex)}
+        if checks and not args.no_cpu_baseline and world == 1:   # (the checkers and the CPU baseline: N = 1 only -- at N > 1 the other ranks would wait ~2 min for rank 0)
             # cpu_baseline AND the parity checker are the INDEPENDENT compiled restatement (oracle/libgkindep.so: nothing of the product
             # linked).  Until round 4 `parity_sample` came from oracle/cpu_ref.cpp, whose JSON reader and Rego evaluator are the product's
             # own host objects -- product against product for the Rego half; that loop is no part of the bench line any more.

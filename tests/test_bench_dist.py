@@ -66,3 +66,29 @@ def test_sharded_bench_at_world_size_two_equals_one_process():
     assert rc == 0 and strong is not None, err[-2000:]
     assert strong["scaling"] == "strong" and strong["config"]["reviews_total"] == 2688 and strong["config"]["reviews_rank0"] == 1344
     assert strong["config"]["global_violating_pairs"] == one["config"]["global_violating_pairs"]
+
+
+def test_plain_run_dumps_the_last_step(tmp_path):
+    """A plain run (neither --full nor --lean) prints the headline line without the legs that take runs of their own, and
+    --dump-outputs writes what the last timed step computed: every object of this small table, the same arrays from one process
+    and from two ranks over the same objects, and as many violating pairs as the --lean line counts."""
+    import numpy as np
+    common = ["--test-hostemu", "--steps", "3", "--warmup", "1"]
+    rc, one, err = _run(["--gpus", "1", "--reviews", "2688", "--dump-outputs", str(tmp_path / "one")] + common)
+    assert rc == 0 and one is not None, err[-2000:]
+    assert one["steps"] == 3 and one["ms_per_step"] > 0 and one["unit"] == "evals/s" and one["higher_is_better"] is True and one["dtype"] == "u32"
+    assert not set(one) & {"roofline", "exchange", "audit_result_totals", "cpu_baseline", "parity_python_oracle", "other_configs"}
+    rc, two, err = _run(["--gpus", "2", "--reviews", "1344", "--dump-outputs", str(tmp_path / "two")] + common)
+    assert rc == 0 and two is not None, err[-2000:]
+    rc, lean, err = _run(["--gpus", "1", "--reviews", "2688", "--lean"] + common)
+    assert rc == 0 and lean is not None, err[-2000:]
+    got = {p.stem: np.load(p) for p in (tmp_path / "one").glob("*.npy")}
+    assert set(got) == {"violations", "autoreject", "sample_objects", "violating_objects_per_constraint", "autoreject_pairs_per_constraint"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    v = got["violations"]
+    assert v.shape == (50, 2688) and (got["sample_objects"] == np.arange(2688)).all()
+    assert v.sum() == got["violating_objects_per_constraint"].sum() == lean["config"]["global_violating_pairs"] > 1000
+    assert (v.sum(axis=1) == got["violating_objects_per_constraint"]).all()
+    assert (got["autoreject"].sum(axis=1) == got["autoreject_pairs_per_constraint"]).all()
+    for name in ("violations", "sample_objects", "violating_objects_per_constraint", "autoreject_pairs_per_constraint"):
+        assert np.array_equal(np.load(tmp_path / "two" / (name + ".npy")), got[name]), name
