@@ -4,6 +4,7 @@
 // compiles the result for gfx950 with hiprtc when the plan is uploaded; tests/native/hostemu.cpp can compile the same
 // text with g++ to validate the generator in the GPU-less container.
 #include "codegen.hpp"
+#include "cursors.hpp"
 #include "chunks.hpp"
 
 #include <algorithm>
@@ -92,13 +93,15 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
       << "GK_CONST_ARRAY uint32_t gk_zero_lo[1] = {0u};\nGK_CONST_ARRAY uint32_t gk_zero_hi[1] = {" << plan.dims.acc_words << "u};\n";
   }
   // result slots kept per 64-review half and kind (kernel_body.inc GK_RES_K), and where each scope's element count lives
-  o << "#define GK_RES_KV " << jit_res_kv(plan) << "\n#define GK_RES_KM " << jit_res_km(plan) << "\n#define GK_N_SCOPES_K " << plan.scopes.size() << "\n"
-    << "GK_CONST_ARRAY uint32_t gk_count_off[" << std::max<size_t>(1, plan.scopes.size()) << "] = {";
-  for (size_t i = 0; i < plan.scopes.size(); i++) o << (i ? "," : "") << plan.scopes[i].count_off << "u";
-  if (plan.scopes.empty()) o << "0u";
-  o << "};\nGK_CONST_ARRAY uint32_t gk_scope_cap[" << std::max<size_t>(1, plan.scopes.size()) << "] = {";
-  for (size_t i = 0; i < plan.scopes.size(); i++) o << (i ? "," : "") << plan.scopes[i].cap << "u";
-  if (plan.scopes.empty()) o << "0u";
+  // (the element scopes only: an alias cursor's loop is bounded by its scope's count -- cursors.hpp)
+  const size_t n_real = plan.n_real_scopes;
+  o << "#define GK_RES_KV " << jit_res_kv(plan) << "\n#define GK_RES_KM " << jit_res_km(plan) << "\n#define GK_N_SCOPES_K " << n_real << "\n"
+    << "GK_CONST_ARRAY uint32_t gk_count_off[" << std::max<size_t>(1, n_real) << "] = {";
+  for (size_t i = 0; i < n_real; i++) o << (i ? "," : "") << plan.scopes[i].count_off << "u";
+  if (n_real == 0) o << "0u";
+  o << "};\nGK_CONST_ARRAY uint32_t gk_scope_cap[" << std::max<size_t>(1, n_real) << "] = {";
+  for (size_t i = 0; i < n_real; i++) o << (i ? "," : "") << plan.scopes[i].cap << "u";
+  if (n_real == 0) o << "0u";
   o << "};\n";
   // ---------------------------------------------------------------------------------------------- phase 1
   // inlined into its single call site (the chunk loop): as a separate function every LDS atomic would first look the
@@ -286,7 +289,11 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
   o << ";\n";
   // the global predicate words are read once; derived global bits (F_STG) update the register copy as well
   for (uint32_t w = 0; w < plan.dims.n_gwords; w++) o << "  uint32_t g" << w << " = acc.load(" << w << "u);\n";
-  struct Loop { uint32_t scope; int depth; int lit; };   // lit: the element index as a literal (preloaded form), -1: a run-time loop variable
+  // scope: the loop's CURSOR (cursors.hpp; the scope table is indexed by cursor) | lit: the element index as a literal (preloaded
+  // form), -1: a run-time loop variable | rt: a run-time loop inside the preloaded form (an alias cursor's loop)
+  struct Loop { uint32_t scope; int depth; int lit; bool rt = false; };
+  const auto scope_of = [&](uint32_t cursor) -> uint32_t { return cursor < plan.cursor_scope.size() ? plan.cursor_scope[cursor] : cursor; };
+  const auto is_alias = [&](uint32_t cursor) { return cursor >= plan.n_real_scopes; };
   std::vector<Loop> stack;
   // PRELOADED form of the staged parts (round 5).  The formulas are LDS-latency bound: every loop of every formula re-reads its
   // scope's element words (an LDS round trip in front of a handful of bit operations; ~450 instructions took 10 k clocks per
@@ -415,7 +422,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
           const uint32_t endins = code[end];
           Conj cj;
           static const bool conj_on = !(getenv("GK_JIT_CONJ") && atoi(getenv("GK_JIT_CONJ")) == 0);   // (A/B aid)
-          if (conj_on && (endins & 0xFF) == F_ENDLOOP && ((endins >> 8) & 0xFF) == c && sc.cap <= 16 && conj_body(a, pc, end, (endins >> 16) & 0xFF, &cj)) {
+          if (conj_on && !is_alias(a) && (endins & 0xFF) == F_ENDLOOP && ((endins >> 8) & 0xFF) == c && sc.cap <= 16 && conj_body(a, pc, end, (endins >> 16) & 0xFF, &cj)) {
             int pd = -1;
             if (b) { pd = var_of(b - 1); if (pd < 0) throw Unsupported("codegen: parent loop not open"); }
             if (!cj.never) {
@@ -454,7 +461,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
             break;
           }
         }
-        if (pre) {
+        if (pre && !is_alias(a)) {
           // every element a copy of the body; the loop's own F_ENDLOOP closes each copy (below)
           const size_t end = loop_end(pc);
           uint64_t nest0 = sc.cap;
@@ -506,14 +513,15 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         uint64_t nest = sc.cap;
         for (const Loop& l : stack) nest *= plan.scopes[l.scope].cap;
         constexpr uint64_t unroll_max = 4;
-        if (sc.cap <= 16 && nest <= unroll_max) {
+        if (sc.cap <= 16 && nest <= unroll_max && !is_alias(a)) {
           o << ind << "{ _Pragma(\"unroll\")\n";
           o << ind << "  for (uint32_t e" << d << " = 0; e" << d << " < " << sc.cap << "u; e" << d << "++) {\n";
         } else {
           // run-time trip count (the wave's largest element count): partially unrolled, so that the LDS reads of several
           // iterations are in flight together instead of one exposed LDS latency per element
           constexpr int dyn_unroll = 1;   // (partial unrolling of the run-time-bounded loops measured slower in round 3: 0.127 / 0.140 against 0.122 ms)
-          o << ind << "{ const uint32_t n" << d << " = GK_UNI(bounds[" << a << "]);\n";
+          // (an alias cursor: always this form, bounded by its scope's count -- not unrolled, not preloaded)
+          o << ind << "{ const uint32_t n" << d << " = GK_UNI(bounds[" << scope_of(a) << "]);\n";
           if (dyn_unroll > 1) o << ind << "  _Pragma(\"unroll " << dyn_unroll << "\")\n";
           o << ind << "  for (uint32_t e" << d << " = 0; e" << d << " < n" << d << "; e" << d << "++) {\n";
         }
@@ -524,14 +532,14 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
           if (pd < 0) throw Unsupported("codegen: parent loop not open");
           o << ind << "    v" << d << " = v" << d << " & (uint32_t)((w" << d << " >> 24) == e" << pd << ");\n";
         }
-        stack.push_back({a, d, -1});
+        stack.push_back({a, d, -1, pre});
         ind += "    ";
         break;
       }
       case F_ENDLOOP: {
         int d = stack.back().depth;
         o << ind << "b" << a << " = b" << a << " | (b" << b << " & v" << d << ");\n";
-        if (pre) { stack.pop_back(); o << ind.substr(0, ind.size() - 2) << "}\n"; return; }
+        if (pre && !stack.back().rt) { stack.pop_back(); o << ind.substr(0, ind.size() - 2) << "}\n"; return; }
         stack.pop_back();
         ind = ind.substr(0, ind.size() - 4);
         o << ind << "  }\n" << ind << "}\n";
@@ -541,7 +549,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         int d = stack.back().depth;
         o << ind << "b" << c << " = b" << c << " | (b" << a << " & b" << b << " & v" << d << ");\n";
         o << ind << "b" << a << " = b" << a << " | (b" << b << " & v" << d << ");\n";
-        if (pre) { stack.pop_back(); o << ind.substr(0, ind.size() - 2) << "}\n"; return; }
+        if (pre && !stack.back().rt) { stack.pop_back(); o << ind.substr(0, ind.size() - 2) << "}\n"; return; }
         stack.pop_back();
         ind = ind.substr(0, ind.size() - 4);
         o << ind << "  }\n" << ind << "}\n";
@@ -557,7 +565,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         auto vid = [&](const Scope& S, int d, uint32_t slot) {
           std::ostringstream x;
           if (scope_packed(S)) x << "((w" << d << " >> " << ELEM_VID_SHIFT << "u) & " << GK_VID_OVERFLOW << "u)";   // word0 of the loop's current element is in a register
-          else if (pre) {
+          else if (pre && [&] { for (const Loop& l : stack) if (l.depth == d) return l.lit >= 0; return false; }()) {
             int lit = -1;
             for (const Loop& l : stack) if (l.depth == d) lit = l.lit;
             const std::string name = "X" + std::to_string(&S - &plan.scopes[0]) + "_" + std::to_string(lit) + "_" + std::to_string(slot);
@@ -603,7 +611,15 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         break;
       }
       case F_END: pc = pc1; break;
-      default: throw Unsupported("codegen: unknown formula op");
+      default: {
+        if (!is_kcmp(op)) throw Unsupported("codegen: unknown formula op");
+        // F_KCMP (cursors.hpp): the relation of two cursors' ordinals = of the two loops' element counters
+        const int da = var_of(b), db = var_of(c);
+        if (da < 0 || db < 0) throw Unsupported("codegen: key relation outside its loops");
+        static const char* const rel[] = {"==", "!=", "<", "<=", ">", ">="};
+        o << ind << "b" << a << " = (uint32_t)(e" << da << " " << rel[op - F_KCMP] << " e" << db << ");\n";
+        break;
+      }
     }
   }
   };
@@ -630,9 +646,9 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         else if (op == F_ENDLOOP || op == F_ENDLOOP2) { weight /= loop_weight; B.cost += (op == F_ENDLOOP2 ? 2 : 1) * weight; }
         else B.cost += weight;
         if (op == F_STG) B.writes.push_back(1ull << 40 | b | (c << 8));
-        if (op == F_STE) B.writes.push_back(2ull << 40 | (uint64_t)b << 16 | c);
+        if (op == F_STE) B.writes.push_back(2ull << 40 | (uint64_t)scope_of(b) << 16 | c);   // (derived element bits belong to the scope, whichever cursor reads them)
         if (op == F_LDG) B.reads.push_back(1ull << 40 | b | (c << 8));
-        if (op == F_LDE) B.reads.push_back(2ull << 40 | (uint64_t)b << 16 | c);
+        if (op == F_LDE) B.reads.push_back(2ull << 40 | (uint64_t)scope_of(b) << 16 | c);
       }
       for (uint64_t r : B.reads) { auto it = writer.find(r); if (it != writer.end() && it->second != bi) B.stage = std::max(B.stage, blks[it->second].stage + 1); }
       for (uint64_t w : B.writes) writer[w] = bi;

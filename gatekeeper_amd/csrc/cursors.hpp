@@ -1,0 +1,25 @@
+// LOOP CURSORS (self-joins).  Shared by the lowering, the code generator and the bytecode interpreter.
+//
+// The formula ops that walk or address elements -- F_LOOP (a, and the parent b - 1), F_ENDLOOP / F_ENDLOOP2, F_LDE / F_STE (b) and
+// F_VEQ's extra word -- name a CURSOR, not a scope: the plan's Scope table is indexed by cursor.  Cursor s below the number of element
+// scopes is scope s's PRIMARY cursor (a plan without a self-join has no other).  The entries behind them are ALIAS cursors, each a
+// copy of its scope's entry -- the same element words, the same count, hence the same loop bound --, for a second loop over a scope
+// whose first loop is still open (`a := cs[_]; b := cs[_]`, lower.cpp Lowerer::open_cursor): the inner loop walks the elements with
+// a counter of its own instead of resetting the outer loop's.  Scopes and aliases share the GK_MAX_SCOPES ids.
+//
+// This header and vm_cursors.inc are not part of the text handed to hiprtc (jit_source.hpp strips the includes): the generated
+// plan code evaluates the relations itself (codegen.cpp), and the text of a plan without a self-join stays what it was.
+#pragma once
+#include <cstdint>
+
+#include "plan.hpp"
+
+namespace gk {
+
+// F_KCMP + CmpOp (one word):  a = (ordinal of cursor b) <CmpOp> (ordinal of cursor c).  Ordinals are array indices: a relation between
+// the keys of two array iterations (`c[i]; c[j]; i != j`, pe.hpp Atom::KEYREL).
+constexpr uint32_t F_KCMP = 18;
+constexpr uint32_t F_KCMP_LAST = F_KCMP + C_GE;
+inline constexpr bool is_kcmp(uint32_t op) { return op >= F_KCMP && op <= F_KCMP_LAST; }
+
+}  // namespace gk

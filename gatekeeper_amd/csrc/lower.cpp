@@ -1,5 +1,6 @@
 // See lower.hpp.
 #include "lower.hpp"
+#include "cursors.hpp"
 
 #include "builtins.hpp"
 #include "regex.hpp"
@@ -25,6 +26,7 @@ Step key_step(const std::string& k) { Step s; s.key = k; return s; }
 SPath mk_path(std::initializer_list<const char*> keys) { SPath p; for (auto k : keys) p.push_back(key_step(k)); return p; }
 
 int ctz32(uint32_t x) { int n = 0; while (!(x & 1)) { x >>= 1; n++; } return n; }
+static int flip_cmp(int op) { return op == C_LT ? C_GT : op == C_LE ? C_GE : op == C_GT ? C_LT : op == C_GE ? C_LE : op; }   // x op y  <=>  y flip(op) x
 FP flag_f(uint32_t mask) { Atom a; a.kind = Atom::FLAG; a.flag = (uint32_t)ctz32(mask); return f_atom(a); }
 
 FP atom_k(Atom::Kind kind, const SPath& p, const Value& k, int cmp = C_EQ) {
@@ -270,7 +272,7 @@ bool path_mentions(const SPath& p, int q) { for (auto& s : p) if (s.iter && s.q 
 bool mentions_q(const FP& f, int q) {
   switch (f->kind) {
     case FNode::T: case FNode::F: return false;
-    case FNode::ATOM: return f->atom.q == q || path_mentions(f->atom.path, q) || path_mentions(f->atom.path2, q);
+    case FNode::ATOM: return f->atom.q == q || f->atom.q2 == q || path_mentions(f->atom.path, q) || path_mentions(f->atom.path2, q);
     case FNode::EXISTS: if (path_mentions(f->base, q)) return true;   // fallthrough to kids
     default: for (auto& k : f->kids) if (mentions_q(k, q)) return true; return false;
   }
@@ -384,7 +386,7 @@ static FP simplify_impl(const FP& f) {
           for (size_t j = 0; j < uniq.size() && !implied; j++) {
             if (j == i) continue;
             const FP& o = uniq[j];
-            if (o->kind == FNode::ATOM && o->atom.kind != Atom::KEYCMP && o->atom.kind != Atom::FLAG) {
+            if (o->kind == FNode::ATOM && o->atom.kind != Atom::KEYCMP && o->atom.kind != Atom::KEYREL && o->atom.kind != Atom::FLAG) {
               if (o->atom.kind == Atom::DEFINED && o->atom.path.size() == k->atom.path.size() && j > i) continue;
               if (is_prefix(k->atom.path, o->atom.path)) implied = true;
               if (o->atom.kind == Atom::VEQ && is_prefix(k->atom.path, o->atom.path2)) implied = true;
@@ -692,7 +694,7 @@ void collect_q(const FP& f, std::vector<int>& order) {
   auto see_path = [&](const SPath& p) { for (auto& s : p) if (s.iter) see(s.q); };
   switch (f->kind) {
     case FNode::T: case FNode::F: return;
-    case FNode::ATOM: see_path(f->atom.path); see_path(f->atom.path2); see(f->atom.q); return;
+    case FNode::ATOM: see_path(f->atom.path); see_path(f->atom.path2); see(f->atom.q); see(f->atom.q2); return;
     case FNode::EXISTS: see(f->q); see_path(f->base);   // fallthrough
     default: for (auto& k : f->kids) collect_q(k, order);
   }
@@ -708,10 +710,11 @@ FP rename_f(const FP& f, const std::map<int, int>& m) {
   switch (f->kind) {
     case FNode::T: case FNode::F: return f;
     case FNode::ATOM: {
-      if (!path_renamed(f->atom.path, m) && !path_renamed(f->atom.path2, m) && !q_renamed(f->atom.q, m)) return f;   // (nothing to rename: shared, not copied)
+      if (!path_renamed(f->atom.path, m) && !path_renamed(f->atom.path2, m) && !q_renamed(f->atom.q, m) && !q_renamed(f->atom.q2, m)) return f;   // (nothing to rename: shared, not copied)
       Atom a = f->atom;
       a.path = rename_path(a.path, m); a.path2 = rename_path(a.path2, m);
       if (a.q >= 0) { auto it = m.find(a.q); if (it != m.end()) a.q = it->second; }
+      if (a.q2 >= 0) { auto it = m.find(a.q2); if (it != m.end()) a.q2 = it->second; }
       return f_atom(a);
     }
     default: {
@@ -762,6 +765,15 @@ struct Lowerer {
   uint32_t n_gbits = 1;                                    // bit 0 = overflow
   uint64_t regs_used = 0;
   std::map<int, uint32_t> looped;                          // quantifier -> scope
+  // LOOP CURSORS.  A loop walks the elements of its scope with a cursor; the loop of a quantifier whose scope already has an
+  // open loop (a self-join: `a := cs[_]; b := cs[_]`) takes an ALIAS cursor of that scope, so that the inner loop does not reset
+  // the outer one.  A scope's primary cursor is the scope id itself; aliases are numbered GK_ALIAS_BASE + k while lowering and
+  // renumbered n_scopes + k once the scopes are known (PlanBuilder::build), sharing the GK_MAX_SCOPES ids with the scopes.
+  static constexpr uint32_t GK_ALIAS_BASE = 128;
+  std::map<int, uint32_t> qcur;                            // looped quantifier -> its cursor
+  std::map<int, uint32_t> qpar;                            // looped quantifier -> its loop's parent argument (1 + parent cursor, 0 = none)
+  std::vector<uint32_t> alias_scope;                       // alias k -> its scope
+  int loop_depth = 0;                                      // open loops of the block being lowered (the VM keeps 8)
   std::set<int> pass;                                      // pass-through quantifiers
   std::map<int, PatStep> wild;                             // wildcard quantifiers (global existentials)
   std::map<std::string, uint32_t> cheap_strings;
@@ -933,20 +945,54 @@ struct Lowerer {
     return -1;
   }
 
+  uint32_t cursor_scope(uint32_t c) const { return c >= GK_ALIAS_BASE ? alias_scope[c - GK_ALIAS_BASE] : c; }
+  // a cursor for a new loop over scope sc: the primary one unless an open loop holds it, else a free alias of sc
+  uint32_t open_cursor(uint32_t sc) {
+    std::set<uint32_t> busy;
+    for (auto& kv : qcur) busy.insert(kv.second);
+    if (!busy.count(sc)) return sc;
+    for (size_t k = 0; k < alias_scope.size(); k++)
+      if (alias_scope[k] == sc && !busy.count(GK_ALIAS_BASE + (uint32_t)k)) return GK_ALIAS_BASE + (uint32_t)k;
+    if (alias_scope.size() >= GK_MAX_SCOPES) unsupported("self-joins need more loop cursors than the plan has ids");
+    alias_scope.push_back(sc);
+    return GK_ALIAS_BASE + (uint32_t)(alias_scope.size() - 1);
+  }
+  // the parent argument of F_LOOP for an iteration over `base`: 1 + the cursor of the enclosing looped quantifier, 0 = none
+  uint32_t parent_of(const SPath& base) {
+    for (int i = (int)base.size() - 1; i >= 0; i--)
+      if (base[i].iter) { if (qcur.count(base[i].q)) return qcur[base[i].q] + 1; break; }
+    return 0;
+  }
+  void enter_loop() { if (loop_depth >= 8) unsupported("loops nested deeper than 8"); loop_depth++; }
+
   int lower_atom(const Atom& a) {
+    if (a.kind == Atom::KEYREL) {
+      // key(q) <cmp> key(q2) of two array iterations: a comparison of the two loop cursors (a review holding an object where the plan
+      // iterates elements never reaches the formulas: RF_REFUSE).  An element's ordinal is its index when its array is the only one
+      // of its pattern (level 0); below that the ordinals run on over all arrays of the pattern in the review (flatten.cpp), so that
+      // only two elements of ONE array -- the same scope under the same parent element -- keep the order of their indices.
+      if (!qcur.count(a.q) || !qcur.count(a.q2)) unsupported("key relation on an object-key iteration");
+      const uint32_t sa = looped[a.q], sb = looped[a.q2];
+      const bool top = scope_level[sa] == 0 && scope_level[sb] == 0;
+      const bool siblings = sa == sb && qpar[a.q] != 0 && qpar[a.q] == qpar[a.q2];
+      if (!top && !siblings) unsupported("key relation between elements of different nested arrays");
+      int r = alloc();
+      emit(finst(F_KCMP + (uint32_t)a.cmp, r, qcur[a.q], qcur[a.q2]));
+      return r;
+    }
     int r = alloc();
     if (a.kind == Atom::FLAG) { emit(finst(F_LDF, r, a.flag)); return r; }
     if (a.kind == Atom::KEYCMP) unsupported("key comparison outside a simple existential");
     if (a.kind == Atom::VEQ) {
-      uint32_t sc[2], slot[2];
+      uint32_t sc[2], slot[2], cu[2];
       const SPath* ps[2] = {&a.path, &a.path2};
       bool root_side = false;
       for (int k = 0; k < 2; k++) {
         int li = last_looped(*ps[k]);
         for (size_t j = li + 1; j < ps[k]->size(); j++) if ((*ps[k])[j].iter) unsupported("join on a nested iteration");
         // a value outside every iteration lives in the ROOT scope (one element per review)
-        if (li < 0) { sc[k] = root_scope(); root_side = true; }
-        else sc[k] = looped[(*ps[k])[li].q];
+        if (li < 0) { sc[k] = root_scope(); root_side = true; cu[k] = sc[k]; }
+        else { sc[k] = looped[(*ps[k])[li].q]; cu[k] = qcur[(*ps[k])[li].q]; }
         Pattern pat = pattern_of(*ps[k]);
         std::string key = pattern_to_string(pat);
         auto it = val_slots[sc[k]].find(key);
@@ -962,15 +1008,16 @@ struct Lowerer {
       }
       if (root_side) {   // the comparison runs inside the (single-trip) loop over the root scope
         int acc = alloc();
+        enter_loop(); loop_depth--;
         emit(finst(F_LOOP, root_scope(), 0, acc));
         emit(finst(F_VEQ, r));
-        emit(sc[0] | (slot[0] << 8) | (sc[1] << 16) | (slot[1] << 24));
+        emit(cu[0] | (slot[0] << 8) | (cu[1] << 16) | (slot[1] << 24));
         emit(finst(F_ENDLOOP, acc, r));
         release(r);
         return acc;
       }
       emit(finst(F_VEQ, r));
-      emit(sc[0] | (slot[0] << 8) | (sc[1] << 16) | (slot[1] << 24));
+      emit(cu[0] | (slot[0] << 8) | (cu[1] << 16) | (slot[1] << 24));
       return r;
     }
     if (a.kind == Atom::DICT) {
@@ -1030,7 +1077,7 @@ struct Lowerer {
         plan.preds.push_back(p);
         plan.pred_patterns.push_back(pat);
       } else eb = it->second;
-      emit(finst(F_LDE, r, sc, eb));
+      emit(finst(F_LDE, r, qcur[b.path[li].q], eb));
       return r;
     }
     Pattern pat = pattern_of(a.path);
@@ -1063,7 +1110,7 @@ struct Lowerer {
       plan.preds.push_back(p);
       plan.pred_patterns.push_back(pat);
     } else bit = it->second;
-    emit(finst(F_LDE, r, sc, bit));
+    emit(finst(F_LDE, r, qcur[a.path[li].q], bit));
     return r;
   }
 
@@ -1115,6 +1162,11 @@ struct Lowerer {
           bool r = a.cmp == C_EQ ? c == 0 : a.cmp == C_NE ? c != 0 : a.cmp == C_LT ? c < 0 : a.cmp == C_LE ? c <= 0 : a.cmp == C_GT ? c > 0 : c >= 0;
           return r ? f_true() : f_false();
         }
+        if (a.kind == Atom::KEYREL && (a.q == q || a.q2 == q)) {   // one side pinned to a member name: a key test on the other side
+          Atom c; c.kind = Atom::KEYCMP; c.k = Value::string(key);
+          if (a.q == q) { c.q = a.q2; c.cmp = flip_cmp(a.cmp); } else { c.q = a.q; c.cmp = a.cmp; }
+          return f_atom(c);
+        }
         a.path = pin_path(a.path);
         a.path2 = pin_path(a.path2);
         return f_atom(a);
@@ -1149,7 +1201,7 @@ struct Lowerer {
     const FP& r0 = rest[0];
     if (r0->kind == FNode::ATOM) {
       const Atom& a = r0->atom;
-      if (a.kind == Atom::KEYCMP || a.kind == Atom::FLAG || a.kind == Atom::VEQ) return false;
+      if (a.kind == Atom::KEYCMP || a.kind == Atom::KEYREL || a.kind == Atom::FLAG || a.kind == Atom::VEQ) return false;
       if (!path_has_q(a.path, q)) return false;
       *out = a;
       return true;
@@ -1166,6 +1218,7 @@ struct Lowerer {
       case FNode::ATOM: {
         auto last_iter = [](const SPath& p) { for (int i = (int)p.size() - 1; i >= 0; i--) if (p[i].iter) return p[i].q; return -1; };
         if (f->atom.kind == Atom::KEYCMP) return f->atom.q == q;
+        if (f->atom.kind == Atom::KEYREL) return f->atom.q == q || f->atom.q2 == q;
         if (last_iter(f->atom.path) == q) return true;
         if (f->atom.kind == Atom::VEQ && last_iter(f->atom.path2) == q) return true;
         return false;
@@ -1229,9 +1282,27 @@ struct Lowerer {
         return lower(simplify(any));
       }
     }
-    for (auto& c : conj) { PatStep tmp; if (key_constraint(c, q, &tmp)) unsupported("correlated iteration over object keys"); }
-    // pass-through: exists q. exists q2 in (.. q ..). body   with nothing else tied to q's element
-    if (conj.size() == 1 && conj[0]->kind == FNode::EXISTS && path_has_q(conj[0]->base, q) && !uses_elem_directly(conj[0]->kids[0], q)) {
+    for (auto& c : conj) {
+      PatStep tmp;
+      if (!key_constraint(c, q, &tmp)) continue;
+      // (tests on member names: q iterates an object's keys, which the cursors -- array ordinals -- cannot relate)
+      std::function<bool(const FP&)> rel = [&](const FP& g) {
+        if (g->kind == FNode::ATOM) return g->atom.kind == Atom::KEYREL && (g->atom.q == q || g->atom.q2 == q);
+        for (auto& k : g->kids) if (rel(k)) return true;
+        return false;
+      };
+      for (auto& d : conj) if (rel(d)) unsupported("key relation on an object-key iteration");
+      unsupported("correlated iteration over object keys");
+    }
+    // pass-through: exists q. exists q2 in (.. q ..). body   with nothing else tied to q's element -- not even a second iteration
+    // below it (`e1 := c.env[i]; e2 := c.env[j]`: both in the SAME container, which only q's loop provides)
+    std::function<bool(const FP&)> iterates_below_q = [&](const FP& g) {
+      if (g->kind == FNode::EXISTS && path_has_q(g->base, q)) return true;
+      for (auto& k : g->kids) if (iterates_below_q(k)) return true;
+      return false;
+    };
+    if (conj.size() == 1 && conj[0]->kind == FNode::EXISTS && path_has_q(conj[0]->base, q) && !uses_elem_directly(conj[0]->kids[0], q) &&
+        !iterates_below_q(conj[0]->kids[0])) {
       pass.insert(q);
       int r = lower_exists(conj[0]);
       pass.erase(q);
@@ -1256,10 +1327,14 @@ struct Lowerer {
         derived_global[key] = bit;
         std::vector<uint32_t> block;
         std::vector<uint32_t>* saved = cur_code;
+        const std::map<int, uint32_t> saved_cur = qcur;
+        const int saved_depth = loop_depth;
         cur_code = &block;
+        qcur.clear(); loop_depth = 0;   // (the block runs on its own: no loop of the enclosing formula is open there)
         int r = lower_exists_loop(f);
         emit(finst(F_STG, r, bit & 0xFF, bit >> 8));
         release(r);
+        qcur = saved_cur; loop_depth = saved_depth;
         cur_code = saved;
         prologue.push_back(block);
       } else bit = it->second;
@@ -1280,9 +1355,14 @@ struct Lowerer {
         std::vector<uint32_t> block;
         std::vector<uint32_t>* saved = cur_code;
         std::map<int, uint32_t> saved_looped = looped;
+        const std::map<int, uint32_t> saved_cur = qcur, saved_par = qpar;
+        const int saved_depth = loop_depth;
         cur_code = &block;
         looped.clear();
         looped[q1] = s1;
+        qcur.clear();
+        qcur[q1] = s1; qpar[q1] = 0;   // (computed over the scope's PRIMARY cursor; read below through whichever cursor q1 has)
+        loop_depth = 1;
         int acc = alloc();
         emit(finst(F_LOOP, s1, 0, acc));
         int r = lower_exists_loop(f);
@@ -1291,11 +1371,12 @@ struct Lowerer {
         release(r);
         release(acc);
         looped = saved_looped;
+        qcur = saved_cur; qpar = saved_par; loop_depth = saved_depth;
         cur_code = saved;
         prologue.push_back(block);
       } else bit = it->second;
       int r = alloc();
-      emit(finst(F_LDE, r, s1, bit));
+      emit(finst(F_LDE, r, qcur[q1], bit));
       return r;
     }
     return lower_exists_loop(f);
@@ -1309,18 +1390,17 @@ struct Lowerer {
     elem.push_back(st);
     // loop registration must precede pattern_of(elem)
     looped[q] = 0;
-    uint32_t sc;
-    try { sc = scope_for(elem); } catch (...) { looped.erase(q); throw; }
+    uint32_t sc, cu;
+    try { sc = scope_for(elem); cu = open_cursor(sc); enter_loop(); } catch (...) { looped.erase(q); throw; }
     looped[q] = sc;
-    uint32_t parent = 0;
-    for (int i = (int)f->base.size() - 1; i >= 0; i--)
-      if (f->base[i].iter) { if (looped.count(f->base[i].q)) parent = looped[f->base[i].q] + 1; break; }
+    const uint32_t parent = parent_of(f->base);
+    qcur[q] = cu; qpar[q] = parent;
     int acc = alloc();
-    emit(finst(F_LOOP, sc, parent, acc));
+    emit(finst(F_LOOP, cu, parent, acc));
     int r = lower(f->kids[0]);
     emit(finst(F_ENDLOOP, acc, r));
     release(r);
-    looped.erase(q);
+    looped.erase(q); qcur.erase(q); loop_depth--;
     return acc;
   }
 
@@ -1336,12 +1416,12 @@ struct Lowerer {
     Step st; st.iter = true; st.q = q;
     elem.push_back(st);
     looped[q] = 0;
-    uint32_t sc;
-    try { sc = scope_for(elem); } catch (...) { looped.erase(q); throw; }
+    uint32_t sc, cu;
+    try { sc = scope_for(elem); cu = open_cursor(sc); enter_loop(); } catch (...) { looped.erase(q); throw; }
     looped[q] = sc;
-    uint32_t parent = 0;
-    for (int i = (int)f->base.size() - 1; i >= 0; i--)
-      if (f->base[i].iter) { if (looped.count(f->base[i].q)) parent = looped[f->base[i].q] + 1; break; }
+    const uint32_t parent = parent_of(f->base);
+    qcur[q] = cu; qpar[q] = parent;
+    struct Close { Lowerer* L; int q; ~Close() { L->qcur.erase(q); L->loop_depth--; } } close{this, q};
     if (f->atleast > 2) {
       // E_k, k > 2: k accumulators c[1..k], c[j] = "at least j elements satisfied the body so far"; per element, from the top:
       // c[j] |= c[j-1] & hit, with hit = body & "the element exists" (its PRESENT bit -- top-level scopes only: a nested
@@ -1351,10 +1431,10 @@ struct Lowerer {
       std::vector<int> c((size_t)k + 1, -1);
       for (int j = k; j >= 2; j--) { c[j] = alloc(); emit(finst(F_CONST, c[j], 0)); }
       c[1] = alloc();
-      emit(finst(F_LOOP, sc, parent, c[1]));
+      emit(finst(F_LOOP, cu, parent, c[1]));
       int r = lower(f->kids[0]);
       int pres = alloc();
-      emit(finst(F_LDE, pres, sc, 0));       // bit 0 of the element word: P_PRESENT
+      emit(finst(F_LDE, pres, cu, 0));       // bit 0 of the element word: P_PRESENT
       emit(finst(F_AND, r, r, pres));
       for (int j = k; j >= 2; j--) {
         emit(finst(F_AND, pres, c[j - 1], r));
@@ -1369,7 +1449,7 @@ struct Lowerer {
     }
     int twice = alloc(), once = alloc();
     emit(finst(F_CONST, twice, 0));
-    emit(finst(F_LOOP, sc, parent, once));
+    emit(finst(F_LOOP, cu, parent, once));
     int r = lower(f->kids[0]);
     emit(finst(F_ENDLOOP2, once, r, twice));
     release(r);
@@ -1757,6 +1837,29 @@ HostPlan PlanBuilder::build(const PlanCaps& caps) {
     else { sc.val_off = off; off += (uint32_t)sc.cap * val_stride(sc.nvals); }
     p.scopes.push_back(sc);
   }
+  // LOOP CURSORS (Lowerer::open_cursor): the device scope table is the CURSOR table -- entry c describes the elements cursor c walks.
+  // The scopes first (primary cursor = scope id), then one entry per alias cursor, a copy of its scope's entry (same words, same
+  // count, hence the same loop bound), so that every op that addresses a cursor reads the table at the cursor.  A plan without a
+  // self-join has no aliases: the same table and the same bytecode as before cursors existed.
+  const uint32_t n_real = (uint32_t)p.scopes.size();
+  p.cursor_scope.clear();
+  for (uint32_t s = 0; s < n_real; s++) p.cursor_scope.push_back((uint8_t)s);
+  if (!L.alias_scope.empty()) {
+    if (n_real + L.alias_scope.size() > GK_MAX_SCOPES) throw Unsupported("unsupported on the device plan: self-joins need more loop cursors than the plan has ids");
+    for (uint32_t sc : L.alias_scope) { p.scopes.push_back(p.scopes[sc]); p.cursor_scope.push_back((uint8_t)sc); }
+    auto fix = [&](uint32_t c) { return c >= Lowerer::GK_ALIAS_BASE ? n_real + (c - Lowerer::GK_ALIAS_BASE) : c; };
+    for (size_t pc = 0; pc < p.code.size(); pc++) {
+      uint32_t& w = p.code[pc];
+      const uint32_t op = w & 0xFF, a = (w >> 8) & 0xFF, b = (w >> 16) & 0xFF, c = w >> 24;
+      switch (op) {
+        case F_LOOP: w = finst(F_LOOP, fix(a), b ? fix(b - 1) + 1 : 0, c); break;
+        case F_LDE: case F_STE: w = finst(op, a, fix(b), c); break;
+        case F_VEQ: { uint32_t& x = p.code[++pc]; x = fix(x & 0xFF) | (x & 0xFF00u) | (fix((x >> 16) & 0xFF) << 16) | (x & 0xFF000000u); break; }
+        default: if (is_kcmp(op)) w = finst(op, a, fix(b), fix(c)); break;
+      }
+    }
+  }
+  p.n_real_scopes = n_real;
   p.dims.n_preds = (uint32_t)p.preds.size();
   p.dims.n_scopes = (uint32_t)p.scopes.size();
   p.dims.n_code = (uint32_t)p.code.size();

@@ -33,7 +33,9 @@ struct PlanCaps {
 struct HostPlan {
   std::vector<Pred> preds;
   std::vector<Pattern> pred_patterns;     // parallel to preds
-  std::vector<Scope> scopes;
+  std::vector<Scope> scopes;               // the CURSOR table: element scopes [0, n_real_scopes), then alias cursors (copies of their scope)
+  std::vector<uint8_t> cursor_scope;      // cursor -> its element scope (identity below n_real_scopes)
+  uint32_t n_real_scopes = 0;
   std::vector<uint32_t> code;
   std::vector<uint32_t> seg_ends;         // code offsets closing each self-contained block (derived-bit blocks, then one per result)
   std::vector<uint8_t> cheap;

@@ -126,6 +126,7 @@ static std::string f_compose_text(const FP& f) {
           if (a.cmp >= KC_PREFIX) return std::string(kcn[a.cmp - KC_PREFIX]) + "(key(q" + std::to_string(a.q) + ")," + to_term_string(a.k) + ")";
           return "key(q" + std::to_string(a.q) + ") " + cmpn[a.cmp] + " " + to_term_string(a.k);
         }
+        case Atom::KEYREL: return "key(q" + std::to_string(a.q) + ") " + cmpn[a.cmp] + " key(q" + std::to_string(a.q2) + ")";
         case Atom::DICT: return "dict(" + p + ": " + dx_to_string(a.dx) + ")";
       }
     }
@@ -202,11 +203,12 @@ FP rn_f(const FP& f, const QMap& m) {
     case FNode::T: case FNode::F: return f;
     case FNode::ATOM: {
       // (most sub-formulas of a renaming mention none of the renamed quantifiers: they are shared, not copied)
-      if (!path_mentions(f->atom.path, m) && !path_mentions(f->atom.path2, m) && !(f->atom.q >= 0 && m.count(f->atom.q))) return f;
+      if (!path_mentions(f->atom.path, m) && !path_mentions(f->atom.path2, m) && !(f->atom.q >= 0 && m.count(f->atom.q)) && !(f->atom.q2 >= 0 && m.count(f->atom.q2))) return f;
       Atom a = f->atom;
       a.path = rn_path(a.path, m);
       a.path2 = rn_path(a.path2, m);
       if (a.q >= 0) { auto it = m.find(a.q); if (it != m.end()) a.q = it->second; }
+      if (a.q2 >= 0) { auto it = m.find(a.q2); if (it != m.end()) a.q2 = it->second; }
       return f_atom(a);
     }
     default: {
@@ -782,6 +784,13 @@ class PE {
           Atom c; c.kind = Atom::KEYCMP; c.q = a->q; c.cmp = op; c.k = b->c;
           return f_atom(c);
         }
+        if (b->kind == SV::KEYOF) {
+          // the keys of two review iterations (`c[i]; c[j]; i != j`): a relation between the two loop cursors on the device, whose
+          // ordinals are the array indices (lower.cpp F_KCMP); member names of an object iteration are refused there
+          if (a->q == b->q) return cmp_holds(0, op) ? f_true() : f_false();
+          Atom c; c.kind = Atom::KEYREL; c.q = a->q; c.q2 = b->q; c.cmp = op;
+          return f_atom(c);
+        }
         break;
       case SV::STRX:
         if (b->kind == SV::CONST) {
@@ -1297,6 +1306,11 @@ class PE {
           if (k->c.is_string()) { SPath p = cur->path; Step st; st.key = k->c.str(); p.push_back(st); fn(sv_path(p), s); return; }
           if (k->c.is_number()) unsupported("numeric index into review data", line);
           return;
+        }
+        if (k->kind == SV::KEYOF) {   // P[k], k the key of an iteration over exactly P: that iteration's element
+          const std::string ps = spath_to_string(cur->path);
+          for (auto& qb : s.quants)
+            if (qb.first == k->q && spath_to_string(qb.second) == ps) { SPath p = cur->path; Step st; st.iter = true; st.q = k->q; p.push_back(st); fn(sv_path(p), s); return; }
         }
         unsupported("review data indexed by a symbolic key", line);
       case SV::OBJ:

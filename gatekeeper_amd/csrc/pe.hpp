@@ -35,6 +35,7 @@ struct FNode;
 struct Atom {
   enum Kind { DEFINED, TRUTHY, CMP, TYPE, STR_PREFIX, STR_SUFFIX, STR_CONTAINS, STR_IN_SET, STR_REGEX, SPLIT_CMP, SPLIT_COUNT,
               COUNT_CMP, FLAG, VEQ, KEYCMP, SPLIT_PREFIX,
+              KEYREL /* key(q) <cmp> key(q2): the keys of two review iterations (self-joins: `c[i]; c[j]; i != j`) */,
               DICT /* leaf-local expression `dx` over the leaf at `path` is true (dexpr.hpp) */ } kind = DEFINED;
   SPath path;
   int cmp = 0;          // CmpOp
@@ -44,7 +45,8 @@ struct Atom {
   int idx = 0;          // SPLIT_CMP component (negative: from end)
   uint32_t flag = 0;    // FLAG: review flag bit index
   SPath path2;          // VEQ
-  int q = -1;           // KEYCMP
+  int q = -1;           // KEYCMP / KEYREL
+  int q2 = -1;          // KEYREL: the right-hand quantifier
   DX dx;                // DICT
   // DICT made by PROMOTING plain row predicates (string tests on one leaf, lower.cpp fold_dict): the formula it stands for, as the
   // device would evaluate it from the leaf's own rows.  The lowering falls back to it when the dictionary cannot take the expression

@@ -4,6 +4,7 @@
 // in the GPU-less build container.  The product library never links the emulator.
 #pragma once
 #include "plan.hpp"
+#include "cursors.hpp"
 
 #if defined(__HIPCC__)
 #define GK_HD __host__ __device__ inline
@@ -634,6 +635,7 @@ GK_HD Results eval_formulas(const PlanView& pv, Acc& acc, uint32_t flags, const 
         else res.err |= v << c;
         break;
       }
+#include "vm_cursors.inc"
       default: return res;   // F_END
     }
   }
