@@ -77,6 +77,7 @@ uint32_t jit_res_k(const HostPlan& plan) { return jit_res_kv(plan) + 2u * jit_re
 
 std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
   std::ostringstream o;
+  const bool sweep = parts <= 2;   // row groups of 128 reviews and more: resident tables of >= 8 192 reviews (engine.cpp)
   std::vector<std::vector<Pred>> classes;
   jit_path_classes(plan, &classes);
   // (GK_BIT: bit 0 of a formula value; the device text defines it as an opaque copy + mask BEFORE this source -- jit_source.hpp jit_res_macros,
@@ -327,14 +328,36 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
       pc++;
     }
   };
+  // value id of slot `slot` of the element loop depth `d` is at (scope S): packed into the element word, a preloaded register, or read in place
+  auto vid = [&](const Scope& S, int d, uint32_t slot) {
+    std::ostringstream x;
+    if (scope_packed(S)) x << "((w" << d << " >> " << ELEM_VID_SHIFT << "u) & " << GK_VID_OVERFLOW << "u)";   // word0 of the loop's current element is in a register
+    else if (pre && [&] { for (const Loop& l : stack) if (l.depth == d) return l.lit >= 0; return false; }()) {
+      int lit = -1;
+      for (const Loop& l : stack) if (l.depth == d) lit = l.lit;
+      const std::string name = "X" + std::to_string(&S - &plan.scopes[0]) + "_" + std::to_string(lit) + "_" + std::to_string(slot);
+      pre_vals[name] = "acc.load(" + std::to_string(S.val_off + (uint32_t)lit * val_stride(S.nvals) + slot) + "u)";
+      x << name;
+    }
+    else x << "acc.load(" << S.val_off << "u + e" << d << " * " << val_stride(S.nvals) << "u + " << slot << "u)";
+    return x.str();
+  };
   // CONJUNCTION bodies (round 5).  Most loops of a compiled policy set ask "does SOME element hold bits b1 & b2 & !b3 .." -- a
   // conjunction of literals of the element's own words (after the string tests became dictionary bits nearly every container loop
   // of the 200-template corpus has that shape).  Evaluated bit by bit that is an extract per literal, a combine per literal and two
   // operations to accumulate, per element; as ONE masked compare per element word -- (w & care) == want, the element's presence bit
   // among the literals, so that the zero word of an absent element fails by itself -- it is two vector operations and a scalar OR.
   // -> care / want per word of the element (index = word), false when the body is anything but such a conjunction.
-  struct Conj { std::vector<uint32_t> care, want; bool never = false; };
-  auto conj_body = [&](uint32_t scope, size_t pc, size_t end, uint32_t result_reg, Conj* out) -> bool {
+  // JOIN bodies (sweep geometry, `join_ok`).  A value join -- "some volume is present, not of kind k, and NAMED as this mount names its
+  // volume" -- is such a conjunction but for one literal: an equality of value ids (F_VEQ) between the id packed into THIS loop's element
+  // word and a value that does not change inside the loop (a slot of an enclosing loop's element).  With X the outer id,
+  //   ((w ^ (X << ELEM_VID_SHIFT)) & (care | idmask << ELEM_VID_SHIFT)) == want
+  // tests the literals and the sixteen id bits in one compare: three vector operations per pair instead of nine.  vid_eq is false for
+  // id 0: equal ids are both zero or neither, so that half is ONE test of X per outer element, ANDed into the finished mask (`veq`:
+  // the other side of the equality).  Bits of the word above the id field (the parent ordinal) are outside the mask.
+  struct Conj { std::vector<uint32_t> care, want; bool never = false; bool veq = false; uint32_t veq_scope = 0, veq_slot = 0; };
+  constexpr uint32_t kVeqLit = ~0u;   // the equality among a body's literals (never negated: its negation is no masked compare)
+  auto conj_body = [&](uint32_t scope, size_t pc, size_t end, uint32_t result_reg, bool join_ok, Conj* out) -> bool {
     struct Lit { uint32_t bit; bool pos; };
     struct Val { int kind = 0; std::vector<Lit> lits; };   // kind 0: unknown, 1: conjunction of lits, 2: constant false, 3: constant true
     std::map<uint32_t, Val> regs;
@@ -355,7 +378,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
     auto neg = [&](const Val& x) -> Val {
       Val r;
       if (x.kind == 2) r.kind = 3; else if (x.kind == 3) r.kind = 2;
-      else if (x.kind == 1 && x.lits.size() == 1) { r.kind = 1; r.lits = {Lit{x.lits[0].bit, !x.lits[0].pos}}; }
+      else if (x.kind == 1 && x.lits.size() == 1 && x.lits[0].bit != kVeqLit) { r.kind = 1; r.lits = {Lit{x.lits[0].bit, !x.lits[0].pos}}; }
       return r;
     };
     while (pc < end) {
@@ -368,6 +391,17 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         case F_NOT: regs[a] = neg(regs[b]); break;
         case F_MOV: regs[a] = regs[b]; break;
         case F_CONST: { Val v; v.kind = (b & 1) ? 3 : 2; regs[a] = v; break; }
+        case F_VEQ: {
+          const uint32_t x = code[pc++];
+          const uint32_t sa = x & 0xFF, la = (x >> 8) & 0xFF, sb = (x >> 16) & 0xFF, lb = x >> 24;
+          if (!join_ok || out->veq || (sa == scope) == (sb == scope)) return false;   // one equality, one side of it this loop's element
+          const uint32_t so = sa == scope ? sb : sa;
+          // this side: the id in the element word; the other: an element loop that is open around this one (not a cursor of a self-join)
+          if (!scope_packed(plan.scopes[scope]) || is_alias(so) || var_of(so) < 0) return false;
+          out->veq = true; out->veq_scope = so; out->veq_slot = sa == scope ? lb : la;
+          Val v; v.kind = 1; v.lits = {Lit{kVeqLit, true}}; regs[a] = v;
+          break;
+        }
         default: return false;   // a nested loop, a join, a derived bit, a global / flag bit, a disjunction: the general form
       }
       if (regs[a].kind == 0) return false;
@@ -378,12 +412,20 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
     out->care.assign(sc.wpe, 0u); out->want.assign(sc.wpe, 0u);
     out->care[0] = 1u; out->want[0] = 1u;   // the element is present
     if (body.kind == 2) { out->never = true; return true; }
+    bool veq_used = false;
     if (body.kind == 1) for (const Lit& l : body.lits) {
+      if (l.bit == kVeqLit) { veq_used = true; continue; }
       const uint32_t w = elem_word_of_bit(l.bit), m = elem_mask_of_bit(l.bit);
       if (w >= sc.wpe) return false;
       if ((out->care[w] & m) && (((out->want[w] & m) != 0) != l.pos)) { out->never = true; return true; }
       out->care[w] |= m;
       if (l.pos) out->want[w] |= m;
+    }
+    out->veq = veq_used;   // (an equality the result does not depend on is dropped with the rest of the dead code)
+    if (veq_used) {
+      constexpr uint32_t idmask = GK_VID_OVERFLOW << ELEM_VID_SHIFT;
+      if (out->care[0] & idmask) return false;   // (a predicate bit inside the id field: not a layout this form knows)
+      out->care[0] |= idmask;
     }
     return true;
   };
@@ -422,12 +464,21 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
           const uint32_t endins = code[end];
           Conj cj;
           static const bool conj_on = !(getenv("GK_JIT_CONJ") && atoi(getenv("GK_JIT_CONJ")) == 0);   // (A/B aid)
-          if (conj_on && !is_alias(a) && (endins & 0xFF) == F_ENDLOOP && ((endins >> 8) & 0xFF) == c && sc.cap <= 16 && conj_body(a, pc, end, (endins >> 16) & 0xFF, &cj)) {
+          static const bool join_on = !(getenv("GK_JIT_JOIN") && atoi(getenv("GK_JIT_JOIN")) == 0);   // (A/B aid: 0 = the text of before at sweep geometry too)
+          // (the join form: in the unrolled parts of the sweep geometry only -- the 64-review text of admission batches is latency-bound
+          //  and stays byte for byte what it was)
+          const bool join_ok = join_on && sweep && pre;
+          if (conj_on && !is_alias(a) && (endins & 0xFF) == F_ENDLOOP && ((endins >> 8) & 0xFF) == c && sc.cap <= 16 && conj_body(a, pc, end, (endins >> 16) & 0xFF, join_ok, &cj)) {
             int pd = -1;
             if (b) { pd = var_of(b - 1); if (pd < 0) throw Unsupported("codegen: parent loop not open"); }
             if (!cj.never) {
               const bool dyn = !(pre || (sc.cap <= 16 && [&] { uint64_t n = sc.cap; for (const Loop& l : stack) n *= plan.scopes[l.scope].cap; return n <= 4; }()));
               o << ind << "{ uint32_t t_ = 0u;\n";
+              std::string xo;   // the join's other side, invariant in this loop
+              if (cj.veq) {
+                xo = vid(plan.scopes[cj.veq_scope], var_of(cj.veq_scope), cj.veq_slot);
+                o << ind << "  const uint32_t xs_ = " << xo << " << " << ELEM_VID_SHIFT << "u;\n";
+              }
               auto term = [&](const std::string& w0name, uint32_t e_lit, bool have_lit, const std::string& evar) {
                 std::string t;
                 for (uint32_t k = 0; k < sc.wpe; k++) {
@@ -437,7 +488,8 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
                   else if (have_lit) wk = "acc.load(" + std::to_string(sc.word_off + e_lit * sc.wpe + k) + "u)";
                   else wk = "acc.load(" + std::to_string(sc.word_off + k) + "u + " + evar + " * " + std::to_string((int)sc.wpe) + "u)";
                   if (!t.empty()) t += " & ";   // (bitwise on purpose: `&&` is control flow -- a divergent branch per element)
-                  t += "(uint32_t)((" + wk + " & " + u(cj.care[k]) + ") == " + u(cj.want[k]) + ")";
+                  if (k == 0 && cj.veq) t += "(uint32_t)(((" + wk + " ^ xs_) & " + u(cj.care[k]) + ") == " + u(cj.want[k]) + ")";
+                  else t += "(uint32_t)((" + wk + " & " + u(cj.care[k]) + ") == " + u(cj.want[k]) + ")";
                 }
                 if (b) t += " & (uint32_t)((" + w0name + " >> 24) == e" + std::to_string(pd) + ")";
                 return t;
@@ -454,7 +506,9 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
                 o << ind << "  const uint32_t nq_ = GK_UNI(bounds[" << a << "]);\n"
                   << ind << "  for (uint32_t eq_ = 0; eq_ < nq_; eq_++) { const uint32_t wq_ = acc.load(" << sc.word_off << "u + eq_ * " << (int)sc.wpe << "u); t_ |= " << term("wq_", 0, false, "eq_") << "; }\n";
               }
-              o << ind << "  b" << c << " = t_; }\n";
+              // (vid_eq: id 0, "no value", equals nothing; and what does not fit the id field equals no packed id)
+              if (cj.veq) o << ind << "  b" << c << " = t_ & (uint32_t)((" << xo << " - 1u) < " << GK_VID_OVERFLOW << "u); }\n";
+              else o << ind << "  b" << c << " = t_; }\n";
             }
             pre_ops += (size_t)sc.cap * 3;
             pc = end + 1;
@@ -562,19 +616,6 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         const Scope& B = plan.scopes[sb];
         int da = var_of(sa), db = var_of(sb);
         if (da < 0 || db < 0) throw Unsupported("codegen: join outside its loops");
-        auto vid = [&](const Scope& S, int d, uint32_t slot) {
-          std::ostringstream x;
-          if (scope_packed(S)) x << "((w" << d << " >> " << ELEM_VID_SHIFT << "u) & " << GK_VID_OVERFLOW << "u)";   // word0 of the loop's current element is in a register
-          else if (pre && [&] { for (const Loop& l : stack) if (l.depth == d) return l.lit >= 0; return false; }()) {
-            int lit = -1;
-            for (const Loop& l : stack) if (l.depth == d) lit = l.lit;
-            const std::string name = "X" + std::to_string(&S - &plan.scopes[0]) + "_" + std::to_string(lit) + "_" + std::to_string(slot);
-            pre_vals[name] = "acc.load(" + std::to_string(S.val_off + (uint32_t)lit * val_stride(S.nvals) + slot) + "u)";
-            x << name;
-          }
-          else x << "acc.load(" << S.val_off << "u + e" << d << " * " << val_stride(S.nvals) << "u + " << slot << "u)";
-          return x.str();
-        };
         o << ind << "b" << a << " = (uint32_t)vid_eq(" << vid(A, da, la) << ", " << vid(B, db, lb) << ");\n";
         break;
       }
@@ -634,6 +675,9 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
     size_t prev = 0;
     for (uint32_t e : plan.seg_ends) { blks.push_back({prev, e, 0, 0, {}, {}}); prev = e; }
     constexpr uint64_t loop_weight = 3;   // cost of a loop body relative to straight-line code
+    static const bool join_sw = !(getenv("GK_JIT_JOIN") && atoi(getenv("GK_JIT_JOIN")) == 0);
+    const bool join_cost = join_sw && sweep && !(getenv("GK_JIT_PRELOAD") && atoi(getenv("GK_JIT_PRELOAD")) == 0);
+    size_t join_until = 0;   // end of the join-form body the scan is in
     std::map<uint64_t, size_t> writer;   // derived bit -> block
     for (size_t bi = 0; bi < blks.size(); bi++) {
       Blk& B = blks[bi];
@@ -641,8 +685,23 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
       for (size_t pc = B.pc0; pc < B.pc1;) {
         uint32_t ins = code[pc++];
         uint32_t op = ins & 0xFF, b = (ins >> 16) & 0xFF, c = ins >> 24;
-        if (op == F_VEQ) { pc++; B.cost += 12 * weight; }
-        else if (op == F_LOOP) { B.cost += 4 * weight; weight *= loop_weight; }
+        if (op == F_VEQ) { pc++; B.cost += (pc < join_until ? 2 : 12) * weight; }   // (in a join-form body: part of the element's one compare)
+        else if (op == F_LOOP) {
+          B.cost += 4 * weight; weight *= loop_weight;
+          // the share cut at sweep geometry gives a join its real cost: a body of own-word literals and one equality becomes one masked
+          // compare per element (conj_body), where the general form pays an extract, two compares and three combines for the equality
+          if (join_cost) {
+            const size_t end = loop_end(pc);
+            size_t n_veq = 0;
+            bool plain = !is_alias((ins >> 8) & 0xFF) && (code[end] & 0xFF) == F_ENDLOOP && scope_packed(plan.scopes[(ins >> 8) & 0xFF]);
+            for (size_t q = pc; q < end && plain; q++) {
+              const uint32_t qop = code[q] & 0xFF;
+              if (qop == F_VEQ) { q++; n_veq++; }
+              else if (qop != F_LDE && qop != F_AND && qop != F_ANDN && qop != F_NOT && qop != F_MOV && qop != F_CONST) plain = false;
+            }
+            if (plain && n_veq == 1) join_until = end;
+          }
+        }
         else if (op == F_ENDLOOP || op == F_ENDLOOP2) { weight /= loop_weight; B.cost += (op == F_ENDLOOP2 ? 2 : 1) * weight; }
         else B.cost += weight;
         if (op == F_STG) B.writes.push_back(1ull << 40 | b | (c << 8));
