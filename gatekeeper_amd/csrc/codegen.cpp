@@ -429,12 +429,260 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
     }
     return true;
   };
+  // DNF form (sweep geometry, `dnf_ok`).  What conj_body refuses because of a disjunction -- "a container that drops none of the
+  // capabilities, or adds one": bit1 & !(bit2 & !bit3 & !bit4) -- and the top-level formulas over the bits of ONE word (a global
+  // predicate word g<k>, or the review flags) are short disjunctions of conjunctions of literals of that word: each term one masked
+  // compare (w & care) == want, the terms ORed.  The compiler keeps compare results as wave masks, so the ORs are scalar operations; and
+  // a value built of compares only has no higher bits, so its test needs no opaque copy (GK_BIT: `cmpv` below).  A term may also hold
+  // registers the run did not compute -- finished loop results -- as opaque literals (`opos` / `oneg`: ANDed outside the compare), and,
+  // in a loop body, the body's one value-id equality (`veq`: the join form's xor, in every term or in none).
+  struct DTerm { uint32_t care = 0, want = 0; uint64_t opos = 0, oneg = 0; bool veq = false; };
+  struct DVal { bool ok = false; std::vector<DTerm> t; };   // ok: known | no term: false | a term without literals: true
+  constexpr size_t kDnfCap = 8;   // terms a value may have, intermediate values included (a cap of 4 refuses "bit1 and one of five", twice in configs[2])
+  const auto d_implies = [](const DTerm& y, const DTerm& x) {   // every literal of x is a literal of y: y | x == x
+    return (x.care & ~y.care) == 0 && ((y.want ^ x.want) & x.care) == 0 && (x.opos & ~y.opos) == 0 && (x.oneg & ~y.oneg) == 0 && (!x.veq || y.veq);
+  };
+  const auto d_norm = [&](DVal* v) -> bool {   // duplicates merged, absorbed terms dropped; false: more terms than the cap
+    std::vector<DTerm> out;
+    for (const DTerm& y : v->t) {
+      bool drop = false;
+      for (const DTerm& x : out) if (d_implies(y, x)) { drop = true; break; }
+      if (drop) continue;
+      out.erase(std::remove_if(out.begin(), out.end(), [&](const DTerm& x) { return d_implies(x, y); }), out.end());
+      out.push_back(y);
+    }
+    v->t.swap(out);
+    if (v->t.size() > kDnfCap) { v->ok = false; v->t.clear(); }
+    return v->ok;
+  };
+  const auto d_or = [&](const DVal& x, const DVal& y) -> DVal {
+    DVal r;
+    if (!x.ok || !y.ok) return r;
+    r.ok = true; r.t = x.t; r.t.insert(r.t.end(), y.t.begin(), y.t.end());
+    d_norm(&r);
+    return r;
+  };
+  const auto d_and = [&](const DVal& x, const DVal& y) -> DVal {
+    DVal r;
+    if (!x.ok || !y.ok) return r;
+    r.ok = true;
+    for (const DTerm& p : x.t) for (const DTerm& q : y.t) {
+      if (((p.want ^ q.want) & p.care & q.care) || (p.opos & q.oneg) || (p.oneg & q.opos)) continue;   // a contradictory term
+      DTerm m;
+      m.care = p.care | q.care; m.want = p.want | q.want; m.opos = p.opos | q.opos; m.oneg = p.oneg | q.oneg; m.veq = p.veq || q.veq;
+      r.t.push_back(m);
+      if (r.t.size() > 4 * kDnfCap && !d_norm(&r)) return r;
+    }
+    d_norm(&r);
+    return r;
+  };
+  const auto d_not = [&](const DVal& x) -> DVal {   // De Morgan: the product over the terms of "one of its literals fails"
+    DVal r;
+    if (!x.ok) return r;
+    r.ok = true; r.t.push_back(DTerm{});
+    for (const DTerm& p : x.t) {
+      DVal alt; alt.ok = true;
+      if (p.veq) return DVal{};   // (the negation of an equality of ids is no masked compare)
+      for (uint32_t k = 0; k < 32; k++) if (p.care >> k & 1u) { DTerm l; l.care = 1u << k; l.want = ~p.want & (1u << k); alt.t.push_back(l); }
+      for (uint32_t k = 0; k < 64; k++) {
+        if (p.opos >> k & 1ull) { DTerm l; l.oneg = 1ull << k; alt.t.push_back(l); }
+        if (p.oneg >> k & 1ull) { DTerm l; l.opos = 1ull << k; alt.t.push_back(l); }
+      }
+      r = d_and(r, alt);
+      if (!r.ok) return r;
+    }
+    return r;
+  };
+  // the straight-line instructions [pc, end) over literals of one word -> the value of every register.  loop_scope >= 0: a loop body
+  // (literals: bits of word 0 of that loop's element; `join`: one value-id equality allowed, its other side an open loop's element --
+  // `open`); -1: a top-level run (literals: bits of one global word or of the flags -- *wkey: which, -1 none yet; registers read before
+  // the run writes them are opaque literals).  *bitops: what the same instructions cost bit by bit (an extract / a connective: 1)
+  struct DJoin { bool veq = false; uint32_t scope = 0, slot = 0; };
+  const auto dnf_eval = [&](int loop_scope, size_t pc, size_t end, bool join, const std::function<bool(uint32_t)>& open, std::map<uint32_t, DVal>* regs,
+                            int* wkey, DJoin* dj, uint32_t* bitops) -> bool {
+    const auto rd = [&](uint32_t r) -> DVal {
+      auto it = regs->find(r);
+      if (it != regs->end()) return it->second;
+      DVal v;
+      if (loop_scope < 0 && r < 64) { v.ok = true; DTerm l; l.opos = 1ull << r; v.t.push_back(l); }
+      return v;
+    };
+    const auto lit = [&](int key, uint32_t mask) -> DVal {
+      DVal v;
+      if (*wkey >= 0 && *wkey != key) return v;
+      *wkey = key;
+      v.ok = true; DTerm l; l.care = mask; l.want = mask; v.t.push_back(l);
+      return v;
+    };
+    while (pc < end) {
+      const uint32_t ins = code[pc++];
+      const uint32_t op = ins & 0xFF, a = (ins >> 8) & 0xFF, b = (ins >> 16) & 0xFF, c = ins >> 24;
+      DVal v;
+      switch (op) {
+        case F_LDG: if (loop_scope >= 0) return false; v = lit((int)((b | (c << 8)) >> 5), 1u << ((b | (c << 8)) & 31)); break;
+        case F_LDF: if (loop_scope >= 0 || b >= 32) return false; v = lit(1 << 20, 1u << b); break;
+        case F_LDE: if (loop_scope < 0 || b != (uint32_t)loop_scope || elem_word_of_bit(c) != 0) return false; v = lit(0, elem_mask_of_bit(c)); break;
+        case F_AND: v = d_and(rd(b), rd(c)); break;
+        case F_OR: v = d_or(rd(b), rd(c)); break;
+        case F_ANDN: v = d_and(rd(b), d_not(rd(c))); break;
+        case F_NOT: v = d_not(rd(b)); break;
+        case F_MOV: v = rd(b); (*bitops)--; break;
+        case F_CONST: v.ok = true; if (b & 1) v.t.push_back(DTerm{}); (*bitops)--; break;
+        case F_VEQ: {
+          const uint32_t x = code[pc++];
+          const uint32_t sa = x & 0xFF, la = (x >> 8) & 0xFF, sb = (x >> 16) & 0xFF, lb = x >> 24;
+          const uint32_t scope = (uint32_t)loop_scope;
+          if (loop_scope < 0 || !join || dj->veq || (sa == scope) == (sb == scope)) return false;
+          const uint32_t so = sa == scope ? sb : sa;
+          if (!scope_packed(plan.scopes[scope]) || is_alias(so) || !open(so)) return false;
+          dj->veq = true; dj->scope = so; dj->slot = sa == scope ? lb : la;
+          v.ok = true; DTerm l; l.veq = true; v.t.push_back(l);
+          (*bitops) += 8;   // (an extract, two compares and three combines, and the other side's extract, as the share cut counts them)
+          break;
+        }
+        default: return false;
+      }
+      (*bitops)++;
+      if (!v.ok) return false;
+      (*regs)[a] = v;
+    }
+    return true;
+  };
+  const auto dnf_cost = [](const std::vector<DTerm>& t) -> uint32_t {   // operations of the form: 2 per compare (3 with the join's xor), the opaque literals' ANDs and negations, the ORs
+    uint32_t n = 0;
+    for (const DTerm& x : t) n += ((x.care || x.veq) ? (x.veq ? 3u : 2u) : 0u) + (uint32_t)__builtin_popcountll(x.opos) + 2u * (uint32_t)__builtin_popcountll(x.oneg);
+    return n + (t.empty() ? 0u : (uint32_t)t.size() - 1u);
+  };
+  // a loop body as a DNF of the loop's element word 0, the presence bit in every term.  false: not such a body, or no cheaper than bit by bit
+  struct DnfLoop { std::vector<DTerm> terms; DJoin dj; uint32_t cost = 0; };
+  const auto dnf_body = [&](uint32_t scope, size_t pc, size_t end, uint32_t result_reg, bool join, const std::function<bool(uint32_t)>& open, DnfLoop* out) -> bool {
+    std::map<uint32_t, DVal> regs;
+    int wkey = -1;
+    uint32_t bitops = 0;
+    if (plan.scopes[scope].wpe == 0 || !dnf_eval((int)scope, pc, end, join, open, &regs, &wkey, &out->dj, &bitops)) return false;
+    auto it = regs.find(result_reg);
+    if (it == regs.end() || !it->second.ok) return false;
+    DVal present; present.ok = true; { DTerm l; l.care = 1u; l.want = 1u; present.t.push_back(l); }
+    const DVal body = d_and(it->second, present);
+    if (!body.ok) return false;
+    size_t n_veq = 0;
+    constexpr uint32_t idmask = GK_VID_OVERFLOW << ELEM_VID_SHIFT;
+    for (const DTerm& x : body.t) { if (x.veq) n_veq++; if (out->dj.veq && (x.care & idmask)) return false; }
+    if (n_veq != 0 && n_veq != body.t.size()) return false;   // (the id-0 test of the join is one AND behind the ORs: the equality is in every term or in none)
+    out->dj.veq = n_veq != 0;
+    out->terms = body.t;
+    out->cost = dnf_cost(body.t);
+    return out->cost < bitops;
+  };
+  // a top-level run: the straight-line instructions from pc up to the first F_RES / F_STG, over the bits of one word and opaque
+  // registers; every register it writes but the result is dead behind it (to the end of the block).  -> the index of that F_RES / F_STG
+  struct DnfRun { std::vector<DTerm> terms; int wkey = -1; size_t at = 0; uint32_t reg = 0, cost = 0; };
+  const auto dnf_run = [&](size_t pc, size_t pc1, DnfRun* out) -> bool {
+    size_t q = pc;
+    for (; q < pc1; q++) {
+      const uint32_t qop = code[q] & 0xFF;
+      if (qop == F_RES || qop == F_STG) break;
+      if (qop != F_LDG && qop != F_LDF && qop != F_AND && qop != F_OR && qop != F_ANDN && qop != F_NOT && qop != F_MOV && qop != F_CONST) return false;
+    }
+    if (q >= pc1 || q == pc) return false;
+    std::map<uint32_t, DVal> regs;
+    DJoin dj;
+    uint32_t bitops = 0;
+    out->wkey = -1;
+    if (!dnf_eval(-1, pc, q, false, [](uint32_t) { return false; }, &regs, &out->wkey, &dj, &bitops)) return false;
+    out->at = q; out->reg = (code[q] >> 8) & 0xFF;
+    auto it = regs.find(out->reg);
+    if (it == regs.end() || !it->second.ok || out->wkey < 0) return false;
+    // liveness: a register the run writes, other than its result, that is read behind the run before it is written again: the general form.
+    // The scan is linear to the end of the block and takes a write inside a later loop body for a write.  That rests on two properties of
+    // the formula code (lower.cpp): a block is self-contained -- no register is carried from one block into another, only derived bits
+    // through F_STE / F_STG -- and a register is only read where every path to the read has written it (a loop's body registers are
+    // written in the body before they are read there; behind the loop only its accumulators, written by F_LOOP itself, are read).  So a
+    // read behind a copy or a loop that did not run never looks for a value of before the loop, the run's temporaries least of all.
+    std::set<uint32_t> pending;
+    for (auto& kv : regs) if (kv.first != out->reg) pending.insert(kv.first);   // (the result register is assigned by the form)
+    for (size_t r = q + 1; r < pc1 && !pending.empty();) {
+      const uint32_t ins = code[r++];
+      const uint32_t op = ins & 0xFF, a = (ins >> 8) & 0xFF, b = (ins >> 16) & 0xFF, c = ins >> 24;
+      std::vector<uint32_t> reads, writes;
+      switch (op) {
+        case F_LDG: case F_LDF: case F_LDE: case F_CONST: writes = {a}; break;
+        case F_AND: case F_OR: case F_ANDN: reads = {b, c}; writes = {a}; break;
+        case F_NOT: case F_MOV: reads = {b}; writes = {a}; break;
+        case F_LOOP: writes = {c}; break;
+        case F_ENDLOOP: reads = {a, b}; writes = {a}; break;
+        case F_ENDLOOP2: reads = {a, b, c}; writes = {a, c}; break;
+        case F_VEQ: r++; writes = {a}; break;
+        case F_RES: case F_STE: case F_STG: reads = {a}; break;
+        case F_END: r = pc1; break;
+        default: if (is_kcmp(op)) writes = {a}; else return false;
+      }
+      for (uint32_t x : reads) if (pending.count(x)) return false;
+      for (uint32_t x : writes) pending.erase(x);
+    }
+    out->terms = it->second.t;
+    out->cost = dnf_cost(out->terms);
+    return out->cost < bitops;
+  };
+  static const bool dnf_on = !(getenv("GK_JIT_DNF") && atoi(getenv("GK_JIT_DNF")) == 0);   // (A/B aid: 0 = the text of before at sweep geometry too)
+  bool cmpv[64] = {};        // COMPARE-VALUED registers of the block being generated: built of compare results and constants only
+  const auto forget_body = [&](size_t pc, size_t end) {   // the registers the instructions [pc, end) write: not compare-valued any more
+    for (size_t q = pc; q < end; q++) {
+      const uint32_t qop = code[q] & 0xFF;
+      if (qop == F_STE || qop == F_STG || qop == F_RES) continue;   // (they write no register)
+      cmpv[(code[q] >> (qop == F_LOOP ? 24 : 8)) & 0xFF] = false;
+      if (qop == F_VEQ) q++;
+    }
+  };
+  // a loop both one-compare forms can take at all: an element loop (no alias cursor) of at most 16 elements that ends in a plain F_ENDLOOP on its own accumulator
+  const auto form_loop = [&](uint32_t scope, uint32_t acc_reg, size_t end) {
+    return !is_alias(scope) && (code[end] & 0xFF) == F_ENDLOOP && ((code[end] >> 8) & 0xFF) == acc_reg && plan.scopes[scope].cap <= 16;
+  };
+  bool run_start = false;    // the next top-level instruction starts a run (block start, behind a loop, behind F_RES / F_STG)
   std::function<void(size_t, size_t, bool, std::string)> gen = [&](size_t pc0, size_t pc1, bool staged, std::string ind) {
   std::ostringstream& o = *out_;
   for (size_t pc = pc0; pc < pc1;) {
     uint32_t ins = code[pc++];
     uint32_t op = ins & 0xFF, a = (ins >> 8) & 0xFF, b = (ins >> 16) & 0xFF, c = ins >> 24;
     pre_ops++;
+    // (the DNF form and the plain tests: in the unrolled parts of the sweep geometry only, as the join form)
+    const bool dnf_ok = dnf_on && sweep && pre && staged;
+    if (dnf_ok && stack.empty() && run_start) {
+      run_start = false;
+      DnfRun rn;
+      if (dnf_run(pc - 1, pc1, &rn)) {
+        const std::string wn = rn.wkey == (1 << 20) ? std::string("flags") : "g" + std::to_string(rn.wkey);
+        bool all_cmp = true;
+        std::string x;
+        for (const DTerm& t : rn.terms) {
+          std::string y;
+          if (t.care) y = "(uint32_t)((" + wn + " & " + u(t.care) + ") == " + u(t.want) + ")";
+          for (uint32_t k = 0; k < 64; k++) {
+            if (t.opos >> k & 1ull) { y += std::string(y.empty() ? "" : " & ") + "b" + std::to_string(k); all_cmp = all_cmp && cmpv[k]; }
+            if (t.oneg >> k & 1ull) { y += std::string(y.empty() ? "" : " & ") + "(b" + std::to_string(k) + " ^ 1u)"; all_cmp = all_cmp && cmpv[k]; }
+          }
+          if (y.empty()) y = "1u";
+          x += std::string(x.empty() ? "" : " | ") + (rn.terms.size() > 1 && (t.opos || t.oneg) ? "(" + y + ")" : y);
+        }
+        if (x.empty()) x = "0u";
+        o << ind << "b" << rn.reg << " = " << x << ";\n";
+        cmpv[rn.reg] = all_cmp;
+        pre_ops += rn.at - pc;
+        pc = rn.at;
+        continue;   // (the run's F_RES / F_STG: below, as ever)
+      }
+    }
+    if (op == F_RES || op == F_STG) run_start = stack.empty();
+    const bool cv_b = b < 64 && cmpv[b], cv_c = c < 64 && cmpv[c];   // (of the operands, before the destination -- often one of them -- changes)
+    if (op == F_LDG || op == F_LDF || op == F_LDE) cmpv[a] = false;
+    else if (op == F_AND || op == F_OR || op == F_ANDN) cmpv[a] = cv_b && cv_c;
+    else if (op == F_NOT || op == F_MOV) cmpv[a] = cv_b;
+    else if (op == F_CONST || op == F_VEQ || is_kcmp(op)) cmpv[a] = true;
+    else if (op == F_LOOP) cmpv[c] = true;   // (b<c> = 0u; a conjunction / join / DNF loop leaves its t_ there, any other its F_ENDLOOP decides)
+    else if (op == F_ENDLOOP) cmpv[a] = false;   // (v<d>: an extract)
+    else if (op == F_ENDLOOP2) { cmpv[a] = false; cmpv[c] = false; }
+    // the test of a formula value: bit 0 through the opaque copy (GK_BIT), but for a compare-valued register -- it has no other bits
+    const auto bit_of = [&](uint32_t r) { return dnf_ok && cmpv[r] ? "b" + std::to_string(r) + " != 0u" : "GK_BIT(b" + std::to_string(r) + ")"; };
     switch (op) {
       case F_LDG: { uint32_t bit = b | (c << 8); o << ind << "b" << a << " = (g" << (bit >> 5) << " >> " << (bit & 31) << ") & 1u;\n"; break; }
       case F_LDF: o << ind << "b" << a << " = (flags >> " << b << ") & 1u;\n"; break;
@@ -468,7 +716,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
           // (the join form: in the unrolled parts of the sweep geometry only -- the 64-review text of admission batches is latency-bound
           //  and stays byte for byte what it was)
           const bool join_ok = join_on && sweep && pre;
-          if (conj_on && !is_alias(a) && (endins & 0xFF) == F_ENDLOOP && ((endins >> 8) & 0xFF) == c && sc.cap <= 16 && conj_body(a, pc, end, (endins >> 16) & 0xFF, join_ok, &cj)) {
+          if (conj_on && form_loop(a, c, end) && conj_body(a, pc, end, (endins >> 16) & 0xFF, join_ok, &cj)) {
             int pd = -1;
             if (b) { pd = var_of(b - 1); if (pd < 0) throw Unsupported("codegen: parent loop not open"); }
             if (!cj.never) {
@@ -512,6 +760,42 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
             }
             pre_ops += (size_t)sc.cap * 3;
             pc = end + 1;
+            run_start = stack.empty();
+            break;
+          }
+          // the DNF form: the terms' compares ORed per element
+          DnfLoop dl;
+          if (dnf_ok && conj_on && form_loop(a, c, end) &&
+              dnf_body(a, pc, end, (endins >> 16) & 0xFF, join_ok, [&](uint32_t so) { return var_of(so) >= 0; }, &dl)) {
+            int pd = -1;
+            if (b) { pd = var_of(b - 1); if (pd < 0) throw Unsupported("codegen: parent loop not open"); }
+            if (!dl.terms.empty()) {
+              o << ind << "{ uint32_t t_ = 0u;\n";
+              std::string xo;
+              if (dl.dj.veq) {
+                xo = vid(plan.scopes[dl.dj.scope], var_of(dl.dj.scope), dl.dj.slot);
+                o << ind << "  const uint32_t xs_ = " << xo << " << " << ELEM_VID_SHIFT << "u;\n";
+              }
+              const bool in_regs = sc.cap <= 8u || stack.empty();
+              for (uint32_t e = 0; e < sc.cap; e++) {
+                std::string wn = "W" + std::to_string(a) + "_" + std::to_string(e), t;
+                if (in_regs) pre_words.insert({a, e});
+                else wn = "wq_";
+                for (const DTerm& x : dl.terms) {
+                  if (!t.empty()) t += " | ";
+                  if (x.veq) t += "(uint32_t)(((" + wn + " ^ xs_) & " + u(x.care | (GK_VID_OVERFLOW << ELEM_VID_SHIFT)) + ") == " + u(x.want) + ")";
+                  else t += "(uint32_t)((" + wn + " & " + u(x.care) + ") == " + u(x.want) + ")";
+                }
+                if (b) t = (dl.terms.size() > 1 ? "(" + t + ")" : t) + " & (uint32_t)((" + wn + " >> 24) == e" + std::to_string(pd) + ")";
+                if (in_regs) o << ind << "  t_ |= " << t << ";\n";
+                else o << ind << "  { const uint32_t wq_ = acc.load(" << (sc.word_off + e * sc.wpe) << "u); t_ |= " << t << "; }\n";
+              }
+              if (dl.dj.veq) o << ind << "  b" << c << " = t_ & (uint32_t)((" << xo << " - 1u) < " << GK_VID_OVERFLOW << "u); }\n";
+              else o << ind << "  b" << c << " = t_; }\n";
+            }
+            pre_ops += (size_t)sc.cap * 3;
+            pc = end + 1;
+            run_start = stack.empty();
             break;
           }
         }
@@ -559,7 +843,9 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
             gen(pc, end + 1, staged, ind + "  ");   // (its F_ENDLOOP pops the stack and closes the copy)
           }
           if (roll) o << ind << "}\n";
+          forget_body(pc, end);   // (a copy that is skipped leaves the body's registers as they were)
           pc = end + 1;
+          run_start = stack.empty();
           break;
         }
         // small capacities: constant trip count, fully unrolled -- the element words of absent elements are zero, so
@@ -595,6 +881,8 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         o << ind << "b" << a << " = b" << a << " | (b" << b << " & v" << d << ");\n";
         if (pre && !stack.back().rt) { stack.pop_back(); o << ind.substr(0, ind.size() - 2) << "}\n"; return; }
         stack.pop_back();
+        run_start = stack.empty();
+        for (bool& x : cmpv) x = false;   // (a run-time loop may not run at all: its registers are what they were)
         ind = ind.substr(0, ind.size() - 4);
         o << ind << "  }\n" << ind << "}\n";
         break;
@@ -605,6 +893,8 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         o << ind << "b" << a << " = b" << a << " | (b" << b << " & v" << d << ");\n";
         if (pre && !stack.back().rt) { stack.pop_back(); o << ind.substr(0, ind.size() - 2) << "}\n"; return; }
         stack.pop_back();
+        run_start = stack.empty();
+        for (bool& x : cmpv) x = false;   // (a run-time loop may not run at all: its registers are what they were)
         ind = ind.substr(0, ind.size() - 4);
         o << ind << "  }\n" << ind << "}\n";
         break;
@@ -626,16 +916,16 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         if (pre && elem_word_of_bit(c) == 0 && pre_words.count({b, (uint32_t)[&] { int lit = -1; for (const Loop& l : stack) if (l.depth == d) lit = l.lit; return lit; }()})) {
           int lit = -1;
           for (const Loop& l : stack) if (l.depth == d) lit = l.lit;
-          o << ind << "if (GK_BIT(b" << a << ")) { acc.or_word(" << sc.word_off << "u + e" << d << " * " << (int)sc.wpe << "u, " << u(elem_mask_of_bit(c)) << "); W" << b << "_" << lit << " |= " << u(elem_mask_of_bit(c)) << "; }\n";
+          o << ind << "if (" << bit_of(a) << ") { acc.or_word(" << sc.word_off << "u + e" << d << " * " << (int)sc.wpe << "u, " << u(elem_mask_of_bit(c)) << "); W" << b << "_" << lit << " |= " << u(elem_mask_of_bit(c)) << "; }\n";
           break;
         }
-        o << ind << "if (GK_BIT(b" << a << ")) acc.or_word(" << sc.word_off << "u + e" << d << " * " << (int)sc.wpe << "u + " << elem_word_of_bit(c) << "u, " << u(elem_mask_of_bit(c)) << ");\n";
+        o << ind << "if (" << bit_of(a) << ") acc.or_word(" << sc.word_off << "u + e" << d << " * " << (int)sc.wpe << "u + " << elem_word_of_bit(c) << "u, " << u(elem_mask_of_bit(c)) << ");\n";
         break;
       }
       case F_STG: {
         uint32_t bit = b | (c << 8);
-        if (staged) o << ind << "if (GK_BIT(b" << a << ")) { g" << (bit >> 5) << " |= " << u(1u << (bit & 31)) << "; acc.or_word(" << (bit >> 5) << "u, " << u(1u << (bit & 31)) << "); }\n";
-        else o << ind << "if (GK_BIT(b" << a << ")) g" << (bit >> 5) << " |= " << u(1u << (bit & 31)) << ";\n";
+        if (staged) o << ind << "if (" << bit_of(a) << ") { g" << (bit >> 5) << " |= " << u(1u << (bit & 31)) << "; acc.or_word(" << (bit >> 5) << "u, " << u(1u << (bit & 31)) << "); }\n";
+        else o << ind << "if (" << bit_of(a) << ") g" << (bit >> 5) << " |= " << u(1u << (bit & 31)) << ";\n";
         break;
       }
       case F_RES: {
@@ -645,7 +935,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         if (staged) {
           const uint32_t kind = (b == 0 && c >= 64) ? 2u + (c >> 6) : b, lane_ = (b == 0) ? (c & 63u) : c;
           if (kind >= 2u + GK_VIOL_WORDS || lane_ >= 64u) throw Unsupported("codegen: result slot out of range");
-          o << ind << "GK_RES(" << kind << ", " << lane_ << ", b" << a << ");\n";
+          o << ind << (dnf_ok && cmpv[a] ? "GK_RESC(" : "GK_RES(") << kind << ", " << lane_ << ", b" << a << ");\n";
           res_slots[kind] |= 1ull << lane_;
         } else if (b == 0) o << ind << "res.viol[" << (c >> 6) << "] |= (uint64_t)b" << a << " << " << (c & 63u) << ";\n";
         else o << ind << "res." << f << " |= (uint64_t)b" << a << " << " << c << ";\n";
@@ -678,14 +968,46 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
     static const bool join_sw = !(getenv("GK_JIT_JOIN") && atoi(getenv("GK_JIT_JOIN")) == 0);
     const bool join_cost = join_sw && sweep && !(getenv("GK_JIT_PRELOAD") && atoi(getenv("GK_JIT_PRELOAD")) == 0);
     size_t join_until = 0;   // end of the join-form body the scan is in
+    // ... and a run or a body that takes the DNF form costs its compares and ORs: the instructions it replaces are free (`free_until`).
+    // The scan keeps `stack` as gen does, so that conj_body / dnf_body decide here exactly as they will there.
+    // (As for the join: the cut is made before `use_pre` is known.  A plan whose unrolled text exceeds `pre_budget` keeps its loops, takes
+    //  neither form, and is then cut with the forms' prices -- a balance a little off, never a wrong result.  The plans in the tree --
+    //  configs[1], [2] and the one-plan corpus -- are all within the budget.)
+    const bool dnf_price = dnf_on && join_cost && !(getenv("GK_JIT_CONJ") && atoi(getenv("GK_JIT_CONJ")) == 0);
+    size_t free_until = 0;
     std::map<uint64_t, size_t> writer;   // derived bit -> block
     for (size_t bi = 0; bi < blks.size(); bi++) {
       Blk& B = blks[bi];
       uint64_t weight = 1;
+      bool rs = true;   // gen's run_start, kept by the same rule: a run starts at the block's first instruction, behind F_RES / F_STG and behind a loop, at top level
+      stack.clear();
       for (size_t pc = B.pc0; pc < B.pc1;) {
         uint32_t ins = code[pc++];
         uint32_t op = ins & 0xFF, b = (ins >> 16) & 0xFF, c = ins >> 24;
-        if (op == F_VEQ) { pc++; B.cost += (pc < join_until ? 2 : 12) * weight; }   // (in a join-form body: part of the element's one compare)
+        if (dnf_price && stack.empty() && rs && pc > free_until) {
+          DnfRun rn;
+          if (dnf_run(pc - 1, B.pc1, &rn)) { B.cost += rn.cost; free_until = rn.at; }
+        }
+        rs = false;
+        if (dnf_price && (op == F_RES || op == F_STG || op == F_ENDLOOP || op == F_ENDLOOP2)) rs = stack.size() <= (op == F_RES || op == F_STG ? 0u : 1u);
+        if (dnf_price && op == F_LOOP) {
+          const uint32_t a = (ins >> 8) & 0xFF;
+          const size_t end = loop_end(pc);
+          const uint32_t endins = code[end];
+          Conj cj;
+          DnfLoop dl;
+          if (pc > free_until && form_loop(a, c, end) &&
+              !conj_body(a, pc, end, (endins >> 16) & 0xFF, true, &cj) &&
+              dnf_body(a, pc, end, (endins >> 16) & 0xFF, true, [&](uint32_t so) { return var_of(so) >= 0; }, &dl)) {
+            B.cost += (uint64_t)dl.cost * weight * loop_weight;
+            free_until = end;
+          }
+          stack.push_back({a, (int)stack.size(), 0});
+        }
+        if (dnf_price && (op == F_ENDLOOP || op == F_ENDLOOP2) && !stack.empty()) stack.pop_back();
+        const bool paid = pc <= free_until && op != F_LOOP && op != F_ENDLOOP && op != F_ENDLOOP2;   // part of a form that is already paid for
+        if (paid) { if (op == F_VEQ) pc++; }
+        else if (op == F_VEQ) { pc++; B.cost += (pc < join_until ? 2 : 12) * weight; }   // (in a join-form body: part of the element's one compare)
         else if (op == F_LOOP) {
           B.cost += 4 * weight; weight *= loop_weight;
           // the share cut at sweep geometry gives a join its real cost: a body of own-word literals and one equality becomes one masked
@@ -844,6 +1166,11 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
       << "#ifndef GK_RES\n#define GK_RES(kind, slot, b) do { if ((kind) == 0) res.viol[0] |= (uint64_t)(b) << (slot); else if ((kind) == 1) res.match |= (uint64_t)(b) << (slot); "
          "else if ((kind) == 2) res.err |= (uint64_t)(b) << (slot); else res.viol[(kind) - 2] |= (uint64_t)(b) << (slot); } while (0)\n#define GK_RES_PROLOGUE\n#endif\n"
          "#ifndef GK_RES_FLUSH\n#define GK_RES_FLUSH(m0, m1, m2, m3, m4, m5)\n#endif\n"
+      // GK_RESC: GK_RES of a compare-valued register -- the ballot tests the whole value, no opaque copy (jit_source.hpp GK_BIT); where the
+      // result words do not ride in lanes (another compiler of this text, GK_JIT_RES_LANES=0) it is GK_RES
+      << (dnf_on && sweep ? std::string("#ifndef GK_RESC\n") + (getenv("GK_JIT_RES_LANES") && atoi(getenv("GK_JIT_RES_LANES")) == 0 ? "#if 0\n" : "#if defined(GK_WRITELANE2) && defined(GK_RES_BASE)\n") +
+                                "#define GK_RESC(kind, slot, b) do { const unsigned long long m_ = __ballot((b) != 0u); GK_WRITELANE2(m_, slot, gk_rl##kind, gk_rh##kind); } while (0)\n"
+                                "#else\n#define GK_RESC(kind, slot, b) GK_RES(kind, slot, b)\n#endif\n#endif\n" : std::string())
       << "template <class Acc>\nGK_HD void jit_formula_part(uint32_t part, Acc& acc, uint32_t flags, const uint8_t* heap, const uint32_t* bounds, Results& res, unsigned long long* masks) {\n"
       << "  (void)heap; (void)flags; (void)bounds; (void)res; (void)masks;\n  GK_RES_PROLOGUE\n  uint32_t";
     for (int i = 0; i < 64; i++) o << (i ? ", " : " ") << "b" << i << " = 0u";
@@ -883,6 +1210,8 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
           out_ = &body; pre = true;
           pre_words.clear(); pre_bounds.clear(); pre_vals.clear();
           stack.clear();
+          for (bool& x : cmpv) x = false;   // (per block: the registers are reused)
+          run_start = true;
           gen(blks[bi].pc0, blks[bi].pc1, true, "      ");
           out_ = &o; pre = false;
           for (uint32_t sidx : pre_bounds) if (bounds_done.insert(sidx).second) { flush(); o << "      const uint32_t ns" << sidx << " = GK_UNI(bounds[" << sidx << "]);\n"; }
