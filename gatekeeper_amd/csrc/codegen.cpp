@@ -321,7 +321,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
     int depth = 0;
     for (;;) {
       const uint32_t op = code[pc] & 0xFF;
-      if (op == F_VEQ) { pc += 2; continue; }
+      if (has_slot_word(op)) { pc += 2; continue; }
       if (op == F_LOOP) depth++;
       if (op == F_ENDLOOP || op == F_ENDLOOP2) { if (depth == 0) return pc; depth--; }
       if (op == F_END) throw Unsupported("codegen: loop without an end");
@@ -329,10 +329,14 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
     }
   };
   // value id of slot `slot` of the element loop depth `d` is at (scope S): packed into the element word, a preloaded register, or read in place
+  // (vid_in_place: an ordering relation reads its unpacked slots where it uses them -- one LDS read with a constant address in an unrolled
+  //  copy -- instead of keeping every element's ids in registers across the part: four relations over a 16-element scope with two
+  //  slots held 32 more registers live and pushed the 256-review text past its budget, 52 bytes of scratch per lane)
+  bool vid_in_place = false;
   auto vid = [&](const Scope& S, int d, uint32_t slot) {
     std::ostringstream x;
     if (scope_packed(S)) x << "((w" << d << " >> " << ELEM_VID_SHIFT << "u) & " << GK_VID_OVERFLOW << "u)";   // word0 of the loop's current element is in a register
-    else if (pre && [&] { for (const Loop& l : stack) if (l.depth == d) return l.lit >= 0; return false; }()) {
+    else if (pre && !vid_in_place && [&] { for (const Loop& l : stack) if (l.depth == d) return l.lit >= 0; return false; }()) {
       int lit = -1;
       for (const Loop& l : stack) if (l.depth == d) lit = l.lit;
       const std::string name = "X" + std::to_string(&S - &plan.scopes[0]) + "_" + std::to_string(lit) + "_" + std::to_string(slot);
@@ -613,6 +617,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         case F_ENDLOOP: reads = {a, b}; writes = {a}; break;
         case F_ENDLOOP2: reads = {a, b, c}; writes = {a, c}; break;
         case F_VEQ: r++; writes = {a}; break;
+        case F_VCMP + C_LT: case F_VCMP + C_LE: case F_VCMP + C_GT: case F_VCMP + C_GE: r++; writes = {a}; break;
         case F_RES: case F_STE: case F_STG: reads = {a}; break;
         case F_END: r = pc1; break;
         default: if (is_kcmp(op)) writes = {a}; else return false;
@@ -631,7 +636,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
       const uint32_t qop = code[q] & 0xFF;
       if (qop == F_STE || qop == F_STG || qop == F_RES) continue;   // (they write no register)
       cmpv[(code[q] >> (qop == F_LOOP ? 24 : 8)) & 0xFF] = false;
-      if (qop == F_VEQ) q++;
+      if (has_slot_word(qop)) q++;
     }
   };
   // a loop both one-compare forms can take at all: an element loop (no alias cursor) of at most 16 elements that ends in a plain F_ENDLOOP on its own accumulator
@@ -677,7 +682,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
     if (op == F_LDG || op == F_LDF || op == F_LDE) cmpv[a] = false;
     else if (op == F_AND || op == F_OR || op == F_ANDN) cmpv[a] = cv_b && cv_c;
     else if (op == F_NOT || op == F_MOV) cmpv[a] = cv_b;
-    else if (op == F_CONST || op == F_VEQ || is_kcmp(op)) cmpv[a] = true;
+    else if (op == F_CONST || op == F_VEQ || is_kcmp(op) || is_vcmp(op)) cmpv[a] = true;
     else if (op == F_LOOP) cmpv[c] = true;   // (b<c> = 0u; a conjunction / join / DNF loop leaves its t_ there, any other its F_ENDLOOP decides)
     else if (op == F_ENDLOOP) cmpv[a] = false;   // (v<d>: an extract)
     else if (op == F_ENDLOOP2) { cmpv[a] = false; cmpv[c] = false; }
@@ -821,7 +826,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
           bool roll = roll_on && !in_regs && sc.cap >= 3;
           if (roll) for (size_t q = pc; q < end; q++) {
             const uint32_t qi = code[q], qop = qi & 0xFF;
-            if (qop == F_VEQ) { q++; continue; }
+            if (has_slot_word(qop)) { q++; continue; }
             if (qop == F_STE && ((qi >> 16) & 0xFF) == a) { roll = false; break; }
           }
           const auto word_at = [&](uint32_t e) { return std::to_string(sc.word_off + e * sc.wpe) + "u"; };
@@ -943,6 +948,21 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
       }
       case F_END: pc = pc1; break;
       default: {
+        if (is_vcmp(op)) {
+          // F_VCMP (cursors.hpp): an ordering relation of two value ids -- ranks -- in the general form, both read as F_VEQ reads them;
+          // an empty slot (0) is in no relation.  (The join and the DNF form decline a body that holds one: their xor is for equality.)
+          const uint32_t x = code[pc++];
+          const uint32_t sa = x & 0xFF, la = (x >> 8) & 0xFF, sb = (x >> 16) & 0xFF, lb = x >> 24;
+          const int da = var_of(sa), db = var_of(sb);
+          if (da < 0 || db < 0) throw Unsupported("codegen: value relation outside its loops");
+          static const char* const vrel[] = {"==", "!=", "<", "<=", ">", ">="};
+          vid_in_place = true;
+          const std::string xa = vid(plan.scopes[sa], da, la), xb = vid(plan.scopes[sb], db, lb);
+          vid_in_place = false;
+          o << ind << "{ const uint32_t xa_ = " << xa << ", xb_ = " << xb << "; b" << a
+            << " = (uint32_t)((xa_ " << vrel[op - F_VCMP] << " xb_) & (xa_ != 0u) & (xb_ != 0u)); }\n";
+          break;
+        }
         if (!is_kcmp(op)) throw Unsupported("codegen: unknown formula op");
         // F_KCMP (cursors.hpp): the relation of two cursors' ordinals = of the two loops' element counters
         const int da = var_of(b), db = var_of(c);
@@ -1006,8 +1026,8 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         }
         if (dnf_price && (op == F_ENDLOOP || op == F_ENDLOOP2) && !stack.empty()) stack.pop_back();
         const bool paid = pc <= free_until && op != F_LOOP && op != F_ENDLOOP && op != F_ENDLOOP2;   // part of a form that is already paid for
-        if (paid) { if (op == F_VEQ) pc++; }
-        else if (op == F_VEQ) { pc++; B.cost += (pc < join_until ? 2 : 12) * weight; }   // (in a join-form body: part of the element's one compare)
+        if (paid) { if (has_slot_word(op)) pc++; }
+        else if (has_slot_word(op)) { pc++; B.cost += (op == F_VEQ && pc < join_until ? 2 : 12) * weight; }   // (in a join-form body: part of the element's one compare)
         else if (op == F_LOOP) {
           B.cost += 4 * weight; weight *= loop_weight;
           // the share cut at sweep geometry gives a join its real cost: a body of own-word literals and one equality becomes one masked
@@ -1019,6 +1039,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
             for (size_t q = pc; q < end && plain; q++) {
               const uint32_t qop = code[q] & 0xFF;
               if (qop == F_VEQ) { q++; n_veq++; }
+              else if (is_vcmp(qop)) plain = false;   // (an ordering relation: the general form)
               else if (qop != F_LDE && qop != F_AND && qop != F_ANDN && qop != F_NOT && qop != F_MOV && qop != F_CONST) plain = false;
             }
             if (plain && n_veq == 1) join_until = end;
@@ -1151,7 +1172,7 @@ std::string generate_plan_source(const HostPlan& plan, uint32_t parts) {
         uint64_t n = 0;
         while (pc < pc1) {
           const uint32_t ins = code[pc], op = ins & 0xFF;
-          if (op == F_VEQ) { pc += 2; n += 2; continue; }
+          if (has_slot_word(op)) { pc += 2; n += 2; continue; }
           if (op == F_LOOP) { const size_t end = loop_end(pc + 1); n += (uint64_t)plan.scopes[(ins >> 8) & 0xFF].cap * (4 + unrolled(pc + 1, end)); pc = end + 1; continue; }
           n++; pc++;
         }

@@ -22,4 +22,13 @@ constexpr uint32_t F_KCMP = 18;
 constexpr uint32_t F_KCMP_LAST = F_KCMP + C_GE;
 inline constexpr bool is_kcmp(uint32_t op) { return op >= F_KCMP && op <= F_KCMP_LAST; }
 
+// F_VCMP + CmpOp (C_LT .. C_GE; followed by F_VEQ's extra word):  a = (value slot A) <CmpOp> (value slot B) under Rego's total order,
+// false when either slot is empty.  The slots hold value ids as for F_VEQ; the ids of a table flattened with an ORDERED value pattern in
+// the registry are RANKS -- id(a) < id(b) iff a < b within the review (flatten.cpp Flattener::rank_review) -- so the relation is one
+// unsigned compare of the two ids.  `==` / `!=` between two review values stay F_VEQ.
+constexpr uint32_t F_VCMP = 24;
+inline constexpr bool is_vcmp(uint32_t op) { return op >= F_VCMP + C_LT && op <= F_VCMP + C_GE; }
+// the ops that carry F_VEQ's extra word: every scan of the formula code steps over it
+inline constexpr bool has_slot_word(uint32_t op) { return op == F_VEQ || is_vcmp(op); }
+
 }  // namespace gk

@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <mutex>
 
@@ -298,14 +299,23 @@ bool DictRegistry::carrier_of(const PathDict& dict, uint32_t elem_path_id, std::
   return false;
 }
 
-bool DictRegistry::add_value(const Pattern& leaf, bool add) {
+bool DictRegistry::add_value(const Pattern& leaf, bool add, bool ordered) {
   const std::string k = pattern_to_string(leaf);
   std::unique_lock<std::shared_mutex> l(mu_);
-  for (auto& g : values_) if (g.first == k) return true;
+  bool have = false, have_ordered = false;
+  for (auto& g : values_) if (g.first == k) { have = true; break; }
+  if (ordered) for (auto& g : ordered_) if (g.first == k) { have_ordered = true; break; }
+  if (have && (!ordered || have_ordered)) return true;
   if (!add) return false;
-  values_.emplace_back(k, leaf);
-  gen_++;   // tables flattened before this do not carry the ids: they are stale (engine.cpp dict_gen)
+  if (!have) values_.emplace_back(k, leaf);
+  if (ordered) { ordered_.emplace_back(k, leaf); n_ordered_.store((uint32_t)ordered_.size(), std::memory_order_release); }
+  gen_++;   // tables flattened before this do not carry the ids -- or carry ids that are no ranks: they are stale (engine.cpp dict_gen)
   return true;
+}
+bool DictRegistry::ordered(const PathDict& dict, uint32_t path_id) const {
+  std::shared_lock<std::shared_mutex> l(mu_);
+  for (const auto& g : ordered_) if (pattern_matches(g.second, dict, path_id)) return true;
+  return false;
 }
 bool DictRegistry::set_reads(const std::vector<Pattern>& pats) {
   std::vector<std::pair<std::string, Pattern>> v;
@@ -875,9 +885,78 @@ uint32_t Flattener::value_id(uint32_t meta, uint32_t lo, uint32_t hi) {
     if (want.tag != 4 || e.off == want.off || memcmp(&t_->heap[e.off], &t_->heap[want.off], (size_t)(want.key >> 32)) == 0) return e.id;
   }
   want.id = GK_VID_FIRST + (uint32_t)vids_.size();
-  if (want.id >= GK_VID_OVERFLOW) return GK_VID_OVERFLOW;   // more distinct compared values than ids: the review is refused where one is needed
+  if (want.id + (ranked() ? 2u : 0u) >= GK_VID_OVERFLOW) return GK_VID_OVERFLOW;   // (ranked ids: the two empty containers sit behind every interned value)
+  if (false) return GK_VID_OVERFLOW;   // more distinct compared values than ids: the review is refused where one is needed
   vids_.push_back(want);
   return want.id;
+}
+
+bool Flattener::ordered_wanted(uint32_t path) {
+  if (!reg_) return false;
+  if (path >= dict_paths_.size()) dict_paths_.resize((size_t)path * 2 + 64);
+  DictPath& d = dict_paths_[path];
+  if (d.ostate == 0) d.ostate = reg_->ordered(*dict_, path) ? 2 : 1;
+  return d.ostate == 2;
+}
+
+// Rego's total order (value.hpp compare) on two interned values: numbers by numeric value, before every string; strings by their bytes,
+// inline and heap strings alike.  Two entries are never equal values (value_id interned them apart) except an inexact number and its
+// exact neighbour, which no ordering relation reads (emit: such a row on an ordered path carries no id).
+int Flattener::vid_order(const VidEnt& a, const VidEnt& b) const {
+  const bool na = a.tag <= 2, nb = b.tag <= 2;
+  if (na != nb) return na ? -1 : 1;
+  if (na) {
+    const auto dbl = [](const VidEnt& e) { double d; memcpy(&d, &e.key, 8); return d; };
+    // an int64 against a double, exactly: against the double's floor, the fraction breaks the tie
+    const auto int_dbl = [](int64_t i, double d) {
+      if (d != d) return -1;
+      if (d >= 9223372036854775808.0) return -1;
+      if (d < -9223372036854775808.0) return 1;
+      const double fl = std::floor(d);
+      const int64_t f = (int64_t)fl;
+      if (i != f) return i < f ? -1 : 1;
+      return d > fl ? -1 : 0;
+    };
+    if (a.tag == 1 && b.tag == 1) { const int64_t x = (int64_t)a.key, y = (int64_t)b.key; return x < y ? -1 : x > y ? 1 : 0; }
+    if (a.tag == 1) return int_dbl((int64_t)a.key, dbl(b));
+    if (b.tag == 1) return -int_dbl((int64_t)b.key, dbl(a));
+    const double x = dbl(a), y = dbl(b);
+    return x < y ? -1 : x > y ? 1 : 0;
+  }
+  uint8_t ia[8], ib[8];
+  const auto bytes = [&](const VidEnt& e, uint8_t* tmp, size_t* n) -> const uint8_t* {
+    if (e.tag == 3) { memcpy(tmp, &e.key, 8); *n = tmp[7]; return tmp; }
+    *n = (size_t)(e.key >> 32);
+    return &t_->heap[e.off];
+  };
+  size_t la, lb;
+  const uint8_t* pa = bytes(a, ia, &la);
+  const uint8_t* pb = bytes(b, ib, &lb);
+  const int c = memcmp(pa, pb, std::min(la, lb));
+  if (c) return c < 0 ? -1 : 1;
+  return la < lb ? -1 : la > lb ? 1 : 0;
+}
+
+// The review's value ids become RANKS: null < false < true keep 1 .. 3, the interned numbers and strings take GK_VID_FIRST .. in Rego's
+// order, the empty array and the empty object follow them (every non-empty container has no id at all).  Equal values keep equal ids,
+// so F_VEQ and the message keys (compared before this runs, by equality alone) see what they saw.
+void Flattener::rank_review() {
+  const uint32_t n = (uint32_t)vids_.size();
+  rank_order_.resize(n);
+  for (uint32_t i = 0; i < n; i++) rank_order_[i] = i;
+  std::sort(rank_order_.begin(), rank_order_.end(), [&](uint32_t x, uint32_t y) {
+    const int c = vid_order(vids_[x], vids_[y]);
+    return c ? c < 0 : x < y;
+  });
+  rank_of_.resize(n);
+  for (uint32_t r = 0; r < n; r++) rank_of_[rank_order_[r]] = GK_VID_FIRST + r;
+  for (size_t i = review_stage0_; i < stage_.size(); i++) {
+    uint32_t& rev = stage_[i].row.rev;
+    const uint32_t id = rev >> ROW_VID_SHIFT;
+    if (id < GK_VID_EMPTY_ARRAY || id >= GK_VID_OVERFLOW) continue;
+    const uint32_t to = id == GK_VID_EMPTY_ARRAY ? GK_VID_FIRST + n : id == GK_VID_EMPTY_OBJECT ? GK_VID_FIRST + n + 1u : rank_of_[id - GK_VID_FIRST];
+    rev = (rev & ROW_REV_MASK) | (to << ROW_VID_SHIFT);
+  }
 }
 
 bool Flattener::key_wanted(uint32_t path) {
@@ -936,9 +1015,12 @@ bool Flattener::emit(uint32_t path, uint32_t meta, uint32_t lo, uint32_t hi, boo
   }
   uint32_t rev = rev_cur_;
   if (pb & PB_VALUE) {
-    const uint32_t vid = value_id(meta, lo, hi);
+    uint32_t vid = value_id(meta, lo, hi);
+    // (an inexact number has no place in the order that its payload could vouch for: on an ordered path it carries no id, and the
+    //  review goes to the host as one with a non-empty container there does)
+    if (vid && (meta & ROW_INEXACT) && ordered_wanted(path)) vid = 0u;
     if (vid == 0u || vid >= GK_VID_OVERFLOW) review_flags_ |= RF_HOST_CAND;
-    rev |= vid << ROW_VID_SHIFT; emit_side_effects_ = true;
+    rev |= vid << ROW_VID_SHIFT; emit_side_effects_ = true; vid_emitted_ = true;
   }
   if (pb & PB_KEY) {   // a message key: equal values within the review (or one without an id) -> review.$dup (finish_review)
     emit_side_effects_ = true;
@@ -1112,6 +1194,7 @@ void Flattener::add(const ReviewDoc& doc, HostTable* out) {
   ctr_touched_.clear();
   review_flags_ = 0;
   vids_.clear();
+  review_stage0_ = stage_.size(); vid_emitted_ = false;
   begin_review_keys();
   const Value& req = doc.request;
   // root + request members (input.review.*)
@@ -1184,6 +1267,7 @@ void Flattener::ns_rows(const Value& ns) {
   }
 }
 void Flattener::finish_tail(int source, HostTable* out) {
+  if (vid_emitted_ && ranked()) rank_review();
   switch (source) {
     case SRC_ORIGINAL: review_flags_ |= RF_SRC_ORIGINAL; break;
     case SRC_GENERATED: review_flags_ |= RF_SRC_GENERATED; break;
@@ -2130,6 +2214,7 @@ int Flattener::add_json_request(const RawReview& r, const NsCache& cache, HostTa
   scratch_keep_.clear();
   review_flags_ = 0;
   vids_.clear();
+  review_stage0_ = stage_.size(); vid_emitted_ = false;
   begin_review_keys();
   if (++review_gen_ == 0) { std::fill(ctr_gen_.begin(), ctr_gen_.end(), 0); review_gen_ = 1; }
   // 1. the envelope: spans of the members normalize_admission_request reads; anything else is dropped (Go decodes into a
@@ -2275,6 +2360,7 @@ int Flattener::add_json(const RawReview& r, const NsCache& cache, HostTable* out
   scratch_keep_.clear();
   review_flags_ = 0;
   vids_.clear();
+  review_stage0_ = stage_.size(); vid_emitted_ = false;
   begin_review_keys();
   if (++review_gen_ == 0) { std::fill(ctr_gen_.begin(), ctr_gen_.end(), 0); review_gen_ = 1; }
   const std::string op = r.operation ? r.operation : "";

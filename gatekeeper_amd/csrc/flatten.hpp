@@ -113,8 +113,14 @@ class DictRegistry {
   bool guarded(const PathDict& dict, uint32_t path_id) const;
   // Compared values: leaf patterns whose rows the loaded constraints compare with other review values (P_STORE).  The
   // flattener gives the rows of matching paths a VALUE ID (plan.hpp ROW_VID_*), unique per distinct value within the review.
-  bool add_value(const Pattern& leaf, bool add = true);        // false: not registered (and add = false)
+  // `ordered`: an ORDERING relation reads the pattern's ids (cursors.hpp F_VCMP).  With one ordered pattern in the registry the flattener
+  // hands out RANKS -- id(a) < id(b) iff a < b under Rego's total order, within the review (Flattener::rank_review) -- on every value
+  // path; marking a pattern ordered makes earlier tables stale (gen) even when it was a value pattern already: ids in order of first
+  // occurrence must never meet an ordering relation.
+  bool add_value(const Pattern& leaf, bool add = true, bool ordered = false);   // false: not registered (and add = false)
   bool valued(const PathDict& dict, uint32_t path_id) const;
+  bool has_ordered() const { return n_ordered_.load(std::memory_order_acquire) != 0; }
+  bool ordered(const PathDict& dict, uint32_t path_id) const;   // (not cached here: the flattener asks once per path, and only for inexact numbers)
   // Message keys (round 4, result counting: pe.hpp Template::count_forms): leaf patterns whose values lead the messages of a
   // per-element violation.  A review in which two rows of such paths hold the SAME value -- or one that is no scalar -- gets the
   // synthetic row  review.$dup : true ; the counting plans then leave the review's pairs to the host renderer.
@@ -148,6 +154,8 @@ class DictRegistry {
   mutable std::shared_mutex mu_;
   std::vector<Pat> pats_;
   std::vector<std::pair<std::string, Pattern>> guards_, values_, keys_;
+  std::vector<std::pair<std::string, Pattern>> ordered_;   // the value patterns an ordering relation reads (a subset of values_)
+  std::atomic<uint32_t> n_ordered_{0};
   struct Carrier { std::string key; Pattern elem; std::string member; };
   std::vector<Carrier> carriers_;
   std::atomic<uint64_t> gen_{0};
@@ -353,7 +361,7 @@ class Flattener {
                    // a column of (nearly) unique values -- image tags pinned by digest, generated names -- only fills the memo: after a window of
                    // 8192 look-ups with fewer than one hit in eight the next seven windows evaluate straight (round 6)
                    uint32_t seen = 0, hits = 0, bypass_left = 0; };
-  struct DictPath { std::unique_ptr<StrMemo> smemo; int state = 0; int gstate = 0; int vstate = 0; int kstate = 0; uint32_t rstate = 0 /* 4 | read_state once known */; int pat = -1; std::unique_ptr<DxStrProg> sprog[2] /* the entries / centries compiled for string values (dexpr.hpp) */; bool facts = false /* the main-space answers go to the review facts row, review.$r.$d */; bool deep = false /* some expression looks inside a container leaf */; std::vector<DictEntry> entries; uint32_t dpath = 0; std::unordered_map<std::string, uint64_t> memo;   // state 0 unknown, 1 none, 2 has entries
+  struct DictPath { std::unique_ptr<StrMemo> smemo; int state = 0; int gstate = 0; int vstate = 0; int ostate = 0 /* an ORDERED value path: 0 unknown, 1 no, 2 yes */; int kstate = 0; uint32_t rstate = 0 /* 4 | read_state once known */; int pat = -1; std::unique_ptr<DxStrProg> sprog[2] /* the entries / centries compiled for string values (dexpr.hpp) */; bool facts = false /* the main-space answers go to the review facts row, review.$r.$d */; bool deep = false /* some expression looks inside a container leaf */; std::vector<DictEntry> entries; uint32_t dpath = 0; std::unordered_map<std::string, uint64_t> memo;   // state 0 unknown, 1 none, 2 has entries
                     int cpat = -1; std::vector<DictEntry> centries; uint32_t cpath = 0; std::unordered_map<std::string, uint64_t> cmemo; /* the counting space: <leaf>.$c */ };
   std::vector<DictPath> dict_paths_;
   void dict_row(uint32_t path, uint32_t meta, const Value& leaf, uint64_t* masks_out = nullptr);   // emits <leaf>.$d / .$c when some registered expression is true (masks_out: hands the two masks back instead)
@@ -401,6 +409,14 @@ class Flattener {
   struct VidEnt { uint64_t key; uint32_t tag, off, id; };   // tag 1 number-as-int64, 2 float bits, 3 inline string, 4 heap string (key = hash32 | len << 32, off = heap offset)
   std::vector<VidEnt> vids_;
   uint32_t value_id(uint32_t meta, uint32_t lo, uint32_t hi);
+  // ORDER-PRESERVING ids (DictRegistry::add_value `ordered`): finish_tail turns the ids of the review's staged rows into ranks
+  bool ranked() const { return reg_ && reg_->has_ordered(); }
+  bool ordered_wanted(uint32_t path);   // does an ordering relation read the rows of `path`? (cached per path)
+  int vid_order(const VidEnt& a, const VidEnt& b) const;   // Rego's total order on two interned values (numbers, strings): -1 / 0 / 1
+  void rank_review();
+  size_t review_stage0_ = 0;           // first staged row of the review being flattened
+  bool vid_emitted_ = false;           // ... one of its rows carries a value id
+  std::vector<uint32_t> rank_order_, rank_of_;
   uint32_t id_object_, id_old_, id_m_, id_ns_;
   struct Ctr { uint32_t path, n; };
   std::vector<Ctr> ctrs_;

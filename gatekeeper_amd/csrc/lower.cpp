@@ -761,6 +761,7 @@ struct Lowerer {
   std::vector<int> scope_level;
   std::vector<std::map<std::string, uint32_t>> elem_bits;  // per scope
   std::vector<std::map<std::string, uint32_t>> val_slots;  // per scope
+  std::set<std::string> ordered_vals;   // patterns of the value slots an ordering relation reads (F_VCMP): their ids must be ranks
   std::vector<uint32_t> scope_nbits;
   uint32_t n_gbits = 1;                                    // bit 0 = overflow
   uint64_t regs_used = 0;
@@ -1000,23 +1001,26 @@ struct Lowerer {
           slot[k] = (uint32_t)val_slots[sc[k]].size();
           if (slot[k] >= 8) unsupported("more than 8 joined values on one element scope");
           val_slots[sc[k]][key] = slot[k];
+          if (a.cmp != C_EQ) ordered_vals.insert(key);
           Pred p{};
           p.op = P_STORE; p.dst = D_ELEM; p.scope = (uint8_t)sc[k]; p.level = (uint8_t)scope_level[sc[k]]; p.bit = (uint16_t)slot[k];
           plan.preds.push_back(p);
           plan.pred_patterns.push_back(pat);
-        } else slot[k] = it->second;
+        } else { slot[k] = it->second; if (a.cmp != C_EQ) ordered_vals.insert(key); }
       }
+      // an ordering relation (pe.cpp compare_f): F_VCMP + CmpOp on the same slots, the operands in the order written
+      const uint32_t vop = a.cmp == C_EQ ? (uint32_t)F_VEQ : F_VCMP + (uint32_t)a.cmp;
       if (root_side) {   // the comparison runs inside the (single-trip) loop over the root scope
         int acc = alloc();
         enter_loop(); loop_depth--;
         emit(finst(F_LOOP, root_scope(), 0, acc));
-        emit(finst(F_VEQ, r));
+        emit(finst(vop, r));
         emit(cu[0] | (slot[0] << 8) | (cu[1] << 16) | (slot[1] << 24));
         emit(finst(F_ENDLOOP, acc, r));
         release(r);
         return acc;
       }
-      emit(finst(F_VEQ, r));
+      emit(finst(vop, r));
       emit(cu[0] | (slot[0] << 8) | (cu[1] << 16) | (slot[1] << 24));
       return r;
     }
@@ -1780,7 +1784,7 @@ HostPlan PlanBuilder::build(const PlanCaps& caps) {
     }
     // rows that are compared with other review values need VALUE IDS: the flattener assigns them on the registered paths
     for (size_t i = 0; i < L.plan.preds.size(); i++)
-      if (L.plan.preds[i].op == P_STORE && !reg_->add_value(L.plan.pred_patterns[i], !frozen_)) throw Unsupported("unsupported on the device plan: needs value ids no loaded constraint registered");
+      if (L.plan.preds[i].op == P_STORE && !reg_->add_value(L.plan.pred_patterns[i], !frozen_, L.ordered_vals.count(pattern_to_string(L.plan.pred_patterns[i])) != 0)) throw Unsupported("unsupported on the device plan: needs value ids no loaded constraint registered");
   }
   // ELEMENT CARRIERS (plan.hpp T_ABSENT, round 6).  A scope's element marker is read from the rows of ONE member of the element instead of
   // the element's own rows, when the registry names a carrier for the element pattern -- or this plan can offer one: a member of the
@@ -1855,7 +1859,10 @@ HostPlan PlanBuilder::build(const PlanCaps& caps) {
         case F_LOOP: w = finst(F_LOOP, fix(a), b ? fix(b - 1) + 1 : 0, c); break;
         case F_LDE: case F_STE: w = finst(op, a, fix(b), c); break;
         case F_VEQ: { uint32_t& x = p.code[++pc]; x = fix(x & 0xFF) | (x & 0xFF00u) | (fix((x >> 16) & 0xFF) << 16) | (x & 0xFF000000u); break; }
-        default: if (is_kcmp(op)) w = finst(op, a, fix(b), fix(c)); break;
+        default:
+          if (is_kcmp(op)) w = finst(op, a, fix(b), fix(c));
+          else if (is_vcmp(op)) { uint32_t& x = p.code[++pc]; x = fix(x & 0xFF) | (x & 0xFF00u) | (fix((x >> 16) & 0xFF) << 16) | (x & 0xFF000000u); }
+          break;
       }
     }
   }

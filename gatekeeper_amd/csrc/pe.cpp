@@ -119,7 +119,7 @@ static std::string f_compose_text(const FP& f) {
         case Atom::SPLIT_COUNT: return "count(split(" + p + ")) " + cmpn[a.cmp] + " " + to_term_string(a.k);
         case Atom::COUNT_CMP: return "count(" + p + ") " + cmpn[a.cmp] + " " + to_term_string(a.k);
         case Atom::FLAG: return "flag" + std::to_string(a.flag);
-        case Atom::VEQ: return p + " === " + spath_to_string(a.path2);
+        case Atom::VEQ: return p + (a.cmp == C_EQ ? std::string(" === ") : std::string(" ") + cmpn[a.cmp] + "v ") + spath_to_string(a.path2);
         case Atom::SPLIT_PREFIX: return "splitprefix(" + p + "," + to_term_string(a.k) + ")";
         case Atom::KEYCMP: {
           static const char* kcn[] = {"startswith", "endswith", "contains", "isname"};
@@ -748,9 +748,9 @@ class PE {
         }
         break;
       case SV::PATH:
-        if (b->kind == SV::PATH && spath_to_string(a->path) == spath_to_string(b->path) && (op == C_EQ || op == C_NE)) {   // a value and itself
+        if (b->kind == SV::PATH && spath_to_string(a->path) == spath_to_string(b->path)) {   // a value and itself
           FP d = f_atom(atom_path(Atom::DEFINED, a->path));
-          return op == C_EQ ? d : f_false();
+          return cmp_holds(0, op) ? d : f_false();
         }
         if (b->kind == SV::CONST) {
           const Value& k = b->c;
@@ -769,9 +769,15 @@ class PE {
           return f_atom(c);
         }
         if (b->kind == SV::PATH) {
-          if (op != C_EQ && op != C_NE) unsupported("ordering comparison between two review values");
           Atom c = atom_path(Atom::VEQ, a->path);
           c.path2 = b->path;
+          if (op != C_EQ && op != C_NE) {
+            // an ORDERING relation under Rego's total order: the same atom carrying its relation, operands in the order written.  The
+            // device compares the two value ids, which are ranks once an ordered pattern is registered (lower.cpp F_VCMP); a missing
+            // side makes the relation false, as it makes the expression undefined
+            c.cmp = op;
+            return f_atom(c);
+          }
           FP eq = f_atom(c);
           if (op == C_EQ) return eq;
           return f_and(f_and(f_atom(atom_path(Atom::DEFINED, a->path)), f_atom(atom_path(Atom::DEFINED, b->path))), f_not(eq));

@@ -568,6 +568,7 @@ GK_HD Results eval_formulas(const PlanView& pv, Acc& acc, uint32_t flags, const 
             if (o == F_LOOP) nest++;
             else if (o == F_ENDLOOP || o == F_ENDLOOP2) nest--;
             else if (o == F_VEQ) pc++;
+#include "vm_cursors_scan.inc"
           }
           break;
         }
