@@ -22,6 +22,8 @@ struct EvalOptions {
   bool detached = false;        // (kernels.hip, internal) an enqueue-only pass that dev_eval_finish never collects: see dev_shard_enqueue
   bool kernel_only = false;     // GK_EVAL_KERNEL_ONLY: no totals kernel behind the dominant one (back-to-back timing of that kernel)
   bool time_each = false;       // GK_EVAL_TIME_EACH: an event pair around EVERY launch (isolated kernel durations) instead of one around all pending ones
+  bool timed = true;            // the launches up to the collecting call are bracketed by one event pair (kernel_ms / fast_kernel_ms); false: an
+                                //   enqueue-only sweep nobody asked the duration of records no event -- the collecting call then reports 0
   bool jit_wait = true;         // wait for the plan-specialised build of the dominant kernel; false (admission batches): never
                                 //   block -- the bytecode kernel serves until the background build has been loaded
 };

@@ -1629,6 +1629,9 @@ int gk_table_eval(gk_engine* e, gk_table* t, uint32_t flags, gk_eval_out** out) 
     opt.want_match = flags & GK_EVAL_WANT_MATCH;
     opt.time_each = (flags & GK_EVAL_TIME_EACH) != 0;
     opt.kernel_only = (flags & GK_EVAL_KERNEL_ONLY) != 0 && (flags & GK_EVAL_ASYNC) != 0;
+    // (timing events only where the caller can want the kernels' duration: an evaluation that launches and collects in one call, or
+    //  enqueue-only launches under one of the two timing flags)
+    opt.timed = !(flags & GK_EVAL_ASYNC) || opt.time_each || opt.kernel_only;
     // an admission batch (small, evaluated once) never waits for a compiler; an audit-sized or resident table does
     opt.jit_wait = t->resident || t->n_reviews >= 8192;
     {

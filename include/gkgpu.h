@@ -210,7 +210,10 @@ typedef struct {
 #define GK_EVAL_NO_DOWNLOAD 2u   /* leave results on the device (timing runs) */
 #define GK_EVAL_WANT_LIST 4u
 #define GK_EVAL_ASYNC 8u         /* enqueue one launch on the default stream and return (out = NULL); the next call
-                                    without this flag synchronises, and reports the average kernel time per launch */
+                                    without this flag synchronises.  Launches enqueued with GK_EVAL_KERNEL_ONLY or GK_EVAL_TIME_EACH
+                                    are timed (kernel_ms / fast_kernel_ms of the collecting call), and so is the launch of a call without
+                                    this flag (the average then covers the launches from the first timed one on); plain enqueue-only
+                                    launches record no event, and a GK_EVAL_COLLECT call behind nothing else reports 0 for both */
 #define GK_EVAL_COLLECT 16u      /* do not launch: synchronise and collect the results of the pending GK_EVAL_ASYNC launches */
 #define GK_EVAL_KERNEL_ONLY 64u  /* with GK_EVAL_ASYNC: enqueue the dominant kernel alone, without the per-constraint totals kernel behind it (timing runs:
                                     consecutive launches of that kernel under ONE event pair -- fast_kernel_ms of the collecting call is then the kernel's
