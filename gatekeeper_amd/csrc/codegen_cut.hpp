@@ -33,12 +33,13 @@ inline std::vector<Blk> price_blocks(const HostPlan& plan, bool sweep, const Jit
   size_t free_until = 0;
   std::map<uint64_t, size_t> writer;   // derived bit -> block
   std::vector<uint32_t> stack;         // the cursors of the open loops
+  std::vector<uint64_t> wstack;        // the weight each open loop multiplied the body's cost by
   const OpenLoop open = [&](uint32_t cursor) { return std::find(stack.begin(), stack.end(), cursor) != stack.end(); };
   for (size_t bi = 0; bi < blks.size(); bi++) {
     Blk& B = blks[bi];
     uint64_t weight = 1;
     bool rs = true;   // a run starts at the block's first instruction, behind F_RES / F_STG and behind a loop, at top level
-    stack.clear();
+    stack.clear(); wstack.clear();
     for (size_t pc = B.pc0; pc < B.pc1;) {
       const FIns i = decode(code[pc++]);
       const uint32_t op = i.op;
@@ -62,12 +63,15 @@ inline std::vector<Blk> price_blocks(const HostPlan& plan, bool sweep, const Jit
       if (paid) { if (has_slot_word(op)) pc++; }
       else if (has_slot_word(op)) { pc++; B.cost += (op == F_VEQ && pc < join_until ? 2 : 12) * weight; }   // (in a join-form body: part of the element's one compare)
       else if (op == F_LOOP) {
-        B.cost += 4 * weight; weight *= kLoopWeight;
+        // (an INDEXED loop -- `cs[0]`, codegen_forms.hpp index_range -- is one copy of its body: straight-line code)
+        const size_t body_end = loop_end(code, pc);
+        const uint64_t mult = sw.preload && index_range(plan, i, pc, body_end).restricted() && unrolled_copies(plan, i, pc, body_end) <= 1u ? 1 : kLoopWeight;
+        B.cost += 4 * weight; weight *= mult; wstack.push_back(mult);
         // the share cut at sweep geometry gives a join its real cost: a body of own-word literals and one equality becomes one masked
         // compare per element (conj_body), where the general form pays an extract, two compares and three combines for the equality
         if (join_cost) { const size_t end = loop_end(code, pc); if (loose_join_body(plan, i.a, pc, end)) join_until = end; }
       }
-      else if (loop_close) { weight /= kLoopWeight; B.cost += (op == F_ENDLOOP2 ? 2 : 1) * weight; }
+      else if (loop_close) { weight /= wstack.empty() ? kLoopWeight : wstack.back(); if (!wstack.empty()) wstack.pop_back(); B.cost += (op == F_ENDLOOP2 ? 2 : 1) * weight; }
       else B.cost += weight;
       if (op == F_STG) B.writes.push_back(1ull << 40 | global_bit(i));
       if (op == F_STE) B.writes.push_back(2ull << 40 | (uint64_t)scope_of(plan, i.b) << 16 | i.c);   // (derived element bits belong to the scope, whichever cursor reads them)
@@ -186,7 +190,7 @@ inline uint64_t unrolled_ops(const HostPlan& plan, size_t pc, size_t pc1) {
   while (pc < pc1) {
     const FIns i = decode(plan.code[pc]);
     if (has_slot_word(i.op)) { pc += 2; n += 2; continue; }
-    if (i.op == F_LOOP) { const size_t end = loop_end(plan.code, pc + 1); n += (uint64_t)plan.scopes[i.a].cap * (4 + unrolled_ops(plan, pc + 1, end)); pc = end + 1; continue; }
+    if (i.op == F_LOOP) { const size_t end = loop_end(plan.code, pc + 1); n += (uint64_t)unrolled_copies(plan, i, pc + 1, end) * (4 + unrolled_ops(plan, pc + 1, end)); pc = end + 1; continue; }
     n++; pc++;
   }
   return n;

@@ -332,6 +332,18 @@ class FormulaEmitter {
               << " = (uint32_t)((xa_ " << kRel[op - F_VCMP] << " xb_) & (xa_ != 0u) & (xb_ != 0u)); }\n";
             break;
           }
+          if (is_kimm(op) || op == F_KEND) {
+            // F_KIMM / F_KEND (cursors.hpp): the loop's element counter against a constant / against the lane's own element count of the
+            // scope, which phase 1 left in the accumulators (read once per run of the preloaded form).  In an unrolled copy the counter is
+            // a literal and F_KIMM folds away; an indexed loop has no other copies (unrolled_loop)
+            const int d = var_of(b);
+            if (d < 0) throw Unsupported("codegen: index test outside its loop");
+            if (op != F_KEND) { o << ind << "b" << a << " = (uint32_t)(e" << d << " " << kRel[op - F_KIMM] << " " << c << "u);\n"; break; }
+            std::string n = "acc.load(" + u(plan.scopes[b].count_off) + ")";
+            if (pre) { const std::string name = "N" + std::to_string(scope_of(plan, b)); pre_vals[name] = n; n = name; }
+            o << ind << "b" << a << " = (uint32_t)(e" << d << " + " << c << "u == " << n << ");\n";
+            break;
+          }
           if (!is_kcmp(op)) throw Unsupported("codegen: unknown formula op");
           // F_KCMP (cursors.hpp): the relation of two cursors' ordinals = of the two loops' element counters
           const int da = var_of(b), db = var_of(c);
@@ -387,7 +399,7 @@ class FormulaEmitter {
     if (op == F_LDG || op == F_LDF || op == F_LDE) cmpv[i.a] = false;
     else if (op == F_AND || op == F_OR || op == F_ANDN) cmpv[i.a] = cv_b && cv_c;
     else if (op == F_NOT || op == F_MOV) cmpv[i.a] = cv_b;
-    else if (op == F_CONST || op == F_VEQ || is_kcmp(op) || is_vcmp(op)) cmpv[i.a] = true;
+    else if (op == F_CONST || op == F_VEQ || is_kcmp(op) || is_vcmp(op) || is_kimm(op) || op == F_KEND) cmpv[i.a] = true;
     else if (op == F_LOOP) cmpv[i.c] = true;   // (b<c> = 0u; a conjunction / join / DNF loop leaves its t_ there, any other its F_ENDLOOP decides)
     else if (op == F_ENDLOOP) cmpv[i.a] = false;   // (v<d>: an extract)
     else if (op == F_ENDLOOP2) { cmpv[i.a] = false; cmpv[i.c] = false; }
@@ -536,6 +548,9 @@ class FormulaEmitter {
     // its word from one of them and requests element e + 2 into it (copy e + 2 runs only when copy e did: the guards are
     // thresholds of one count).  Not when the body stores derived bits into this scope's words (a later copy must see them).
     bool roll = JitSwitches::roll() && !in_regs && sc.cap >= 3;
+    // an INDEXED loop (codegen_forms.hpp index_range): the copies of the elements its body can hold for, read where they are used
+    const IndexRange ir = index_range(plan, loop, pc, end);
+    if (ir.restricted()) roll = false;
     if (roll) for (size_t q = pc; q < end; q = next_ins(code, q)) {
       const FIns qi = decode(code[q]);
       if (qi.op == F_STE && qi.b == a) { roll = false; break; }
@@ -543,6 +558,7 @@ class FormulaEmitter {
     const auto word_at = [&](uint32_t e) { return std::to_string(sc.word_off + e * sc.wpe) + "u"; };
     if (roll) o << ind << "{ uint32_t P" << d << "a = acc.load(" << word_at(0) << "), P" << d << "b = acc.load(" << word_at(1) << ");\n";
     for (uint32_t e = 0; e < sc.cap; e++) {
+      if (e < ir.lo || e >= ir.hi) continue;   // (beyond the capacity the element is not in LDS, and the review has overflowed anyway)
       if (in_regs) pre_words.insert({a, e});
       o << ind << (guarded ? "if (" + std::to_string(e) + "u < ns" + std::to_string(a) + ") " : std::string()) << "{\n";
       o << ind << "  constexpr uint32_t e" << d << " = " << e << "u; (void)e" << d << ";\n";

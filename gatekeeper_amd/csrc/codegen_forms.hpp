@@ -328,6 +328,59 @@ inline LoopClass classify_loop(const HostPlan& plan, const FIns& loop, size_t pc
   return lc;
 }
 
+// INDEXED loops.  `cs[0]` is an iteration whose body's top-level conjunction ties the loop's own ordinal to a constant (F_KIMM ==, < or
+// <= on the loop's primary cursor, cursors.hpp): every other element fails the body whatever it holds.  In the unrolled form only the
+// copies of the elements [lo, hi) are written -- one copy for `== k` -- where the general form writes one per element of the capacity.
+// Sound because a skipped copy would add nothing: its body is false, so F_ENDLOOP / F_ENDLOOP2 accumulate nothing, and a body that
+// stores a derived bit or a result (F_STE / F_STG / F_RES) is declined.  `!=`, `>`, `>=`, F_KEND (the count is the lane's own) and alias
+// cursors keep every copy.  The conjunction, join and DNF forms decline a body that holds one of these ops (conj_body / dnf_eval).
+struct IndexRange { uint32_t lo = 0, hi = ~0u; bool restricted() const { return lo != 0 || hi != ~0u; } };
+inline IndexRange index_range(const HostPlan& plan, const FIns& loop, size_t pc, size_t end) {
+  IndexRange r;
+  const std::vector<uint32_t>& code = plan.code;
+  if (is_alias(plan, loop.a)) return r;
+  bool has = false;
+  struct At { size_t pc; int depth; };
+  std::vector<At> ins;
+  int depth = 0;
+  for (size_t q = pc; q < end; q = next_ins(code, q)) {
+    const uint32_t op = code[q] & 0xFF;
+    if (op == F_STE || op == F_STG || op == F_RES) return r;
+    if (op == F_ENDLOOP || op == F_ENDLOOP2) depth--;
+    ins.push_back({q, depth});
+    if (op == F_LOOP) depth++;
+    if (is_kimm(op)) has = true;
+  }
+  if (!has) return r;
+  // the conjuncts of register `reg` as it stands in front of instruction index `before`: through the ANDs and moves of the body's top level
+  const std::function<void(uint32_t, size_t)> visit = [&](uint32_t reg, size_t before) {
+    for (size_t k = before; k-- > 0;) {
+      const FIns i = decode(code[ins[k].pc]);
+      const RegUse use = reg_use(i);
+      if (std::find(use.writes.begin(), use.writes.end(), reg) == use.writes.end()) continue;
+      if (ins[k].depth != 0 || i.op == F_LOOP) return;   // (the result of a nested loop: a conjunct of its own)
+      if (i.op == F_AND) { visit(i.b, k); visit(i.c, k); }
+      else if (i.op == F_MOV) visit(i.b, k);
+      else if (is_kimm(i.op) && i.b == loop.a) {
+        const uint32_t rel = i.op - F_KIMM;
+        if (rel == C_EQ) { r.lo = std::max(r.lo, i.c); r.hi = std::min(r.hi, i.c + 1u); }
+        else if (rel == C_LT) r.hi = std::min(r.hi, i.c);
+        else if (rel == C_LE) r.hi = std::min(r.hi, i.c + 1u);
+      }
+      return;
+    }
+  };
+  visit(decode(code[end]).b, ins.size());
+  return r;
+}
+// copies of a loop's body in the unrolled form
+inline uint32_t unrolled_copies(const HostPlan& plan, const FIns& loop, size_t pc, size_t end) {
+  const uint32_t cap = plan.scopes[loop.a].cap;
+  const IndexRange r = index_range(plan, loop, pc, end);
+  const uint32_t hi = std::min(r.hi, cap);
+  return r.lo < hi ? hi - r.lo : 0u;
+}
+
 // The share cut's own, LOOSER recogniser of a join body (it sets the scan's `join_until`): a plain loop over a packed scope whose body is
 // own-word literals, connectives and exactly one F_VEQ.  It does not look at the equality's sides -- whether one is this loop's element
 // and the other an open loop's -- and so takes a few bodies conj_body refuses; their F_VEQ is then priced as part of the element's one

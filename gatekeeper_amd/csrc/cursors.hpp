@@ -31,4 +31,11 @@ inline constexpr bool is_vcmp(uint32_t op) { return op >= F_VCMP + C_LT && op <=
 // the ops that carry F_VEQ's extra word: every scan of the formula code steps over it
 inline constexpr bool has_slot_word(uint32_t op) { return op == F_VEQ || is_vcmp(op); }
 
+// F_KIMM + CmpOp (one word):  a = (ordinal of cursor b) <CmpOp> c, with c an 8-bit constant: the index of an array element against a
+// number (`cs[0]`, `cs[i]; i > 0`, pe.hpp Atom::KEYCMP).  Only on the cursors of top-level scopes, whose ordinals are the indices.
+constexpr uint32_t F_KIMM = 30;
+inline constexpr bool is_kimm(uint32_t op) { return op >= F_KIMM && op <= F_KIMM + C_GE; }
+// F_KEND (one word):  a = (ordinal of cursor b) + c == the element count of cursor b's scope: element c from the end (`cs[count(cs) - c]`).
+constexpr uint32_t F_KEND = 36;
+
 }  // namespace gk

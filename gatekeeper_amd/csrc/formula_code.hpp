@@ -42,7 +42,7 @@ inline RegUse reg_use(const FIns& i) {
     case F_ENDLOOP2: r.reads = {i.a, i.b, i.c}; r.writes = {i.a, i.c}; break;
     case F_RES: case F_STE: case F_STG: r.reads = {i.a}; break;
     case F_END: break;
-    default: if (is_vcmp(i.op) || is_kcmp(i.op)) r.writes = {i.a}; else r.known = false;
+    default: if (is_vcmp(i.op) || is_kcmp(i.op) || is_kimm(i.op) || i.op == F_KEND) r.writes = {i.a}; else r.known = false;
   }
   return r;
 }

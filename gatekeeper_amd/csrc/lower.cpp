@@ -983,6 +983,21 @@ struct Lowerer {
     }
     int r = alloc();
     if (a.kind == Atom::FLAG) { emit(finst(F_LDF, r, a.flag)); return r; }
+    if (a.kind == Atom::KEYCMP && a.k.is_number() && a.cmp <= (int)C_GE && qcur.count(a.q)) {
+      // the index of an array element against a constant (`cs[0]`, `cs[i]; i > 0`: F_KIMM) or counted from the end (`cs[count(cs) - m]`:
+      // F_KEND) -- a test of the loop cursor's ordinal, which is the index for the first array of a path only: below an iteration the
+      // ordinals run on over all arrays of the pattern (see the key relations above)
+      if (scope_level[looped[a.q]] != 0) unsupported("numeric index into a nested array");
+      const bool big = a.k.i > 255;
+      // constants beyond 255: a review with an array of more than 255 elements never reaches the formulas (its rows carry
+      // ROW_ORD_OVERFLOW and it is answered by the host evaluator), so every ordinal seen here is below such a constant -- `== k` is
+      // false and `< k` true.  A negative constant is below every ordinal.
+      if (a.idx != 0) { if (big) emit(finst(F_CONST, r, 0)); else emit(finst(F_KEND, r, qcur[a.q], (uint32_t)a.k.i)); return r; }
+      if (a.k.i < 0) emit(finst(F_CONST, r, a.cmp == C_NE || a.cmp == C_GT || a.cmp == C_GE));
+      else if (big) emit(finst(F_CONST, r, a.cmp == C_NE || a.cmp == C_LT || a.cmp == C_LE));
+      else emit(finst(F_KIMM + (uint32_t)a.cmp, r, qcur[a.q], (uint32_t)a.k.i));
+      return r;
+    }
     if (a.kind == Atom::KEYCMP) unsupported("key comparison outside a simple existential");
     if (a.kind == Atom::VEQ) {
       uint32_t sc[2], slot[2], cu[2];
@@ -1161,7 +1176,8 @@ struct Lowerer {
         Atom a = f->atom;
         if (a.kind == Atom::KEYCMP && a.q == q) {
           if (a.cmp >= KC_PREFIX) return key_pred_holds(KeyPred{(uint8_t)a.cmp, false, a.k.is_string() ? a.k.str() : std::string()}, key, false) ? f_true() : f_false();
-          if (!a.k.is_string()) return a.cmp == C_NE ? f_true() : f_false();
+          // (a member name against a number: never equal, and above it in Rego's total order; it is no array index counted from the end)
+          if (!a.k.is_string()) return a.idx == 0 && (a.cmp == C_NE || a.cmp == C_GT || a.cmp == C_GE) ? f_true() : f_false();
           int c = key.compare(a.k.str());
           bool r = a.cmp == C_EQ ? c == 0 : a.cmp == C_NE ? c != 0 : a.cmp == C_LT ? c < 0 : a.cmp == C_LE ? c <= 0 : a.cmp == C_GT ? c > 0 : c >= 0;
           return r ? f_true() : f_false();
@@ -1861,6 +1877,7 @@ HostPlan PlanBuilder::build(const PlanCaps& caps) {
         case F_VEQ: { uint32_t& x = p.code[++pc]; x = fix(x & 0xFF) | (x & 0xFF00u) | (fix((x >> 16) & 0xFF) << 16) | (x & 0xFF000000u); break; }
         default:
           if (is_kcmp(op)) w = finst(op, a, fix(b), fix(c));
+          else if (is_kimm(op) || op == F_KEND) w = finst(op, a, fix(b), c);
           else if (is_vcmp(op)) { uint32_t& x = p.code[++pc]; x = fix(x & 0xFF) | (x & 0xFF00u) | (fix((x >> 16) & 0xFF) << 16) | (x & 0xFF000000u); }
           break;
       }

@@ -1,6 +1,7 @@
 // Partial evaluator -- see pe.hpp.
 #include "pe.hpp"
 
+#include <cmath>
 #include <functional>
 #include <set>
 #include <sstream>
@@ -124,6 +125,7 @@ static std::string f_compose_text(const FP& f) {
         case Atom::KEYCMP: {
           static const char* kcn[] = {"startswith", "endswith", "contains", "isname"};
           if (a.cmp >= KC_PREFIX) return std::string(kcn[a.cmp - KC_PREFIX]) + "(key(q" + std::to_string(a.q) + ")," + to_term_string(a.k) + ")";
+          if (a.idx != 0) return "key(q" + std::to_string(a.q) + ") + " + to_term_string(a.k) + " == count";   // (the from-end index, pe.hpp)
           return "key(q" + std::to_string(a.q) + ") " + cmpn[a.cmp] + " " + to_term_string(a.k);
         }
         case Atom::KEYREL: return "key(q" + std::to_string(a.q) + ") " + cmpn[a.cmp] + " key(q" + std::to_string(a.q2) + ")";
@@ -784,9 +786,22 @@ class PE {
         }
         break;
       case SV::KEYOF:
+        if (b->kind == SV::CONST && b->c.is_number() && op != C_EQ && op != C_NE) {
+          // `i < k` on the key of an iteration: array indices are integers, so a fractional bound folds EXACTLY onto the integer next
+          // to it (i < 1.5 is i <= 1, i > 1.5 is i >= 2); the lowering relates the loop cursor's ordinal to the constant (F_KIMM)
+          Atom c; c.kind = Atom::KEYCMP; c.q = a->q; c.cmp = op; c.k = b->c;
+          if (!b->c.is_int) {
+            if (!std::isfinite(b->c.d) || std::fabs(b->c.d) > 1e9) unsupported("comparison of an iteration's key with a bound beyond every index");
+            const bool below = op == C_LT || op == C_LE;
+            c.cmp = below ? C_LE : C_GE;
+            c.k = Value::integer((i128)(below ? std::floor(b->c.d) : std::ceil(b->c.d)));
+          }
+          return f_atom(c);
+        }
         if (b->kind == SV::CONST && (op == C_EQ || op == C_NE)) {
           // member names are strings, array indices numbers: anything else can never be equal
           if (!b->c.is_string() && !b->c.is_number()) return op == C_EQ ? f_false() : f_true();
+          if (b->c.is_number() && !b->c.is_int) return op == C_EQ ? f_false() : f_true();   // (no key is a fraction)
           Atom c; c.kind = Atom::KEYCMP; c.q = a->q; c.cmp = op; c.k = b->c;
           return f_atom(c);
         }
@@ -1282,6 +1297,31 @@ class PE {
     }
   }
 
+  // P[k] / P[count(P) - k] on review data: an iteration over P's children whose key is tied to the constant -- the element loop of an
+  // unbound `P[_]` plus one condition on its cursor (Atom::KEYCMP with a number; lower.cpp F_KIMM / F_KEND).  Only the FIRST array of a
+  // path has ordinals that are indices.  The same index used twice in one state binds one element: the
+  // quantifier of the earlier use, found by its condition, is taken again.
+  void index_elem(const SVP& cur, const Value& k, bool from_end, const State& s, int line, const std::function<void(const SVP&, const State&)>& fn) {
+    for (const Step& st : cur->path) if (st.iter) unsupported("numeric index into a nested array", line);
+    const std::string ps = spath_to_string(cur->path);
+    int q = -1;
+    for (const FP& c : s.conds) {
+      if (c->kind != FNode::ATOM || c->atom.kind != Atom::KEYCMP || c->atom.cmp != C_EQ || (c->atom.idx != 0) != from_end || !c->atom.k.is_number() || compare(c->atom.k, k) != 0) continue;
+      for (auto& qb : s.quants) if (qb.first == c->atom.q && spath_to_string(qb.second) == ps) q = qb.first;
+    }
+    State n = s;
+    if (q < 0) {
+      q = fresh();
+      n.quants.emplace_back(q, cur->path);
+      Atom a; a.kind = Atom::KEYCMP; a.q = q; a.cmp = C_EQ; a.k = k; a.idx = from_end ? 1 : 0;
+      n.conds.push_back(f_atom(a));
+    }
+    SPath p = cur->path;
+    Step st; st.iter = true; st.q = q;
+    p.push_back(st);
+    fn(sv_path(p), n);
+  }
+
   // cur[k]
   void index(const SVP& cur, const SVP& k, const State& s, int line, const std::function<void(const SVP&, const State&)>& fn) {
     switch (cur->kind) {
@@ -1310,7 +1350,18 @@ class PE {
       case SV::PATH:
         if (k->kind == SV::CONST) {
           if (k->c.is_string()) { SPath p = cur->path; Step st; st.key = k->c.str(); p.push_back(st); fn(sv_path(p), s); return; }
-          if (k->c.is_number()) unsupported("numeric index into review data", line);
+          // P[k]: element k of the array P (negative or fractional: undefined, as for a constant array)
+          if (k->c.is_number() && k->c.is_int && k->c.i >= 0) index_elem(cur, k->c, false, s, line, fn);
+          return;
+        }
+        if (k->kind == SV::COUNTOF && spath_to_string(k->path) == spath_to_string(cur->path)) return;   // P[count(P)]: never defined
+        if (k->kind == SV::DERIVED && k->idx != 1 && k->dx->kind == DExpr::ARITH && (k->dx->name == "-" || k->dx->name == "+") &&
+            k->dx->args[0]->kind == DExpr::CALL && k->dx->args[0]->name == "count" && k->dx->args[0]->args.size() == 1 &&
+            k->dx->args[0]->args[0]->kind == DExpr::LEAF && k->dx->args[1]->kind == DExpr::CONST && k->dx->args[1]->c.is_number() && k->dx->args[1]->c.is_int) {
+          // P[count(P) - m]: element m from the end.  count() of ANOTHER path is no index the plan can take
+          if (spath_to_string(k->path) != spath_to_string(cur->path)) unsupported("index counted on another review value", line);
+          const i128 m = k->dx->name == "-" ? k->dx->args[1]->c.i : -k->dx->args[1]->c.i;
+          if (m > 0) index_elem(cur, Value::integer(m), true, s, line, fn);   // (m <= 0: at or beyond the end, undefined)
           return;
         }
         if (k->kind == SV::KEYOF) {   // P[k], k the key of an iteration over exactly P: that iteration's element

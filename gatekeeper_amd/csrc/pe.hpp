@@ -42,7 +42,8 @@ struct Atom {
   Value k;              // constant operand (CMP / STR_* / SPLIT_* / COUNT_CMP / KEYCMP; STR_IN_SET: set/array of strings)
   uint32_t mask = 0;    // TYPE: bit per RowType
   char cut = 0, sep = 0;
-  int idx = 0;          // SPLIT_CMP component (negative: from end)
+  int idx = 0;          // SPLIT_CMP component (negative: from end) | KEYCMP with a NUMBER k: 0 = key(q) <cmp> k, the index of an array
+                        // element against a constant (`cs[0]`, `cs[i]; i > 0`); 1 = key(q) + k == count of q's array (`cs[count(cs) - k]`)
   uint32_t flag = 0;    // FLAG: review flag bit index
   SPath path2;          // VEQ
   int q = -1;           // KEYCMP / KEYREL

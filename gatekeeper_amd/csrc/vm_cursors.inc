@@ -20,3 +20,16 @@
         B = (B & ~(1ull << a)) | ((uint64_t)v << a);
         break;
       }
+      // (cursors.hpp) F_KIMM + CmpOp: reg a = ordinal of cursor b <CmpOp> the constant c
+      case F_KIMM + C_EQ: case F_KIMM + C_NE: case F_KIMM + C_LT: case F_KIMM + C_LE: case F_KIMM + C_GT: case F_KIMM + C_GE: {
+        const uint32_t i = cur[b], rel = op - F_KIMM;
+        const bool v = rel == C_EQ ? i == c : rel == C_NE ? i != c : rel == C_LT ? i < c : rel == C_LE ? i <= c : rel == C_GT ? i > c : i >= c;
+        B = (B & ~(1ull << a)) | ((uint64_t)v << a);
+        break;
+      }
+      // (cursors.hpp) F_KEND: reg a = ordinal of cursor b + c == the element count of its scope (the review's own: max ordinal + 1)
+      case F_KEND: {
+        const bool v = cur[b] + c == acc.load(pv.scopes[b].count_off);
+        B = (B & ~(1ull << a)) | ((uint64_t)v << a);
+        break;
+      }
