@@ -39,7 +39,7 @@ EXPORTS = [
     "gk_constraint_add", "gk_constraint_remove", "gk_data_put", "gk_data_remove", "gk_excluder_replace", "gk_excluder_excluded", "gk_table_create", "gk_table_free",
     "gk_table_eval", "gk_eval_free", "gk_render", "gk_render_error", "gk_free", "gk_dump", "gk_table_topk", "gk_topk_free",
     "gk_table_totals", "gk_totals_free", "gk_table_get_stats", "gk_batcher_start", "gk_batcher_stop", "gk_query", "gk_query_ex", "gk_query_ex2",
-    "gk_resident_sweep", "gk_sweep_free", "gk_resident_review", "gk_resident_review_ex",
+    "gk_resident_sweep", "gk_sweep_free", "gk_resident_review", "gk_resident_review_ex", "gk_resident_audit", "gk_audit_free",
     "gk_comm_unique_id", "gk_comm_init", "gk_comm_destroy", "gk_comm_info", "gk_table_sweep_sharded", "gk_shard_free",
     "gk_jit_quiesce", "gk_jit_cache_stats", "gk_jit_cache_dir", "gk_jit_cache_drop_memory", "gk_host_cpus", "gk_table_create_spool", "gk_spool_info_free", "gk_debug_set",
     # include/gksynth.h (bench / test plumbing)
@@ -98,6 +98,13 @@ class gk_sweep_out(C.Structure):
     _fields_ = [("n_objects", C.c_uint64), ("n_constraints", C.c_uint32), ("n_chunks", C.c_uint32), ("constraint_ids", C.POINTER(C.c_uint32)),
                 ("pairs", C.POINTER(C.c_uint64)), ("results", C.POINTER(C.c_uint64)), ("flattened", C.c_uint64), ("beyond_limits", C.c_uint64),
                 ("sync_s", C.c_double), ("eval_s", C.c_double)]
+
+
+class gk_audit_out(C.Structure):
+    _fields_ = [("n_objects", C.c_uint64), ("n_constraints", C.c_uint32), ("stride", C.c_uint32), ("n_chunks", C.c_uint32),
+                ("constraint_ids", C.POINTER(C.c_uint32)), ("pairs", C.POINTER(C.c_uint64)), ("results", C.POINTER(C.c_uint64)),
+                ("counts", C.POINTER(C.c_uint32)), ("objects", C.POINTER(C.c_uint32)), ("overflow", C.POINTER(C.c_uint32)),
+                ("n_paths", C.c_uint32), ("paths", C.POINTER(C.c_char_p)), ("beyond_limits", C.c_uint64), ("err_pairs", C.POINTER(C.c_uint64))]
 
 
 class gk_shard_out(C.Structure):
@@ -223,6 +230,9 @@ def load(hostemu: bool | None = None):
     lib.gk_sweep_free.argtypes = [C.POINTER(gk_sweep_out)]
     lib.gk_sweep_free.restype = None
     lib.gk_resident_review.argtypes = [vp, C.POINTER(cp), sz, C.POINTER(vp)]
+    lib.gk_resident_audit.argtypes = [vp, u32, u32, C.POINTER(C.POINTER(gk_audit_out))]
+    lib.gk_audit_free.argtypes = [C.POINTER(gk_audit_out)]
+    lib.gk_audit_free.restype = None
     lib.gk_batcher_start.argtypes = [vp, C.POINTER(gk_batch_opts)]
     lib.gk_batcher_stop.argtypes = [vp]
     lib.gk_batcher_stop.restype = None

@@ -70,6 +70,13 @@ void dev_eval(const DevPlan* p, const DevTable* t, const EvalOptions& opt, EvalO
 // uses the bitmaps of the table's most recent evaluation.  idx: [nc][cap], n: [nc], ovf: [nc]
 void dev_topk(const DevTable* t, uint32_t nc, const std::vector<uint32_t>& order, const std::vector<uint32_t>& grp, uint32_t k, uint32_t cap,
               std::vector<uint32_t>* idx, std::vector<uint32_t>* n, std::vector<uint32_t>* ovf);
+// resident-set audit lists: dev_topk's selection (same tie rule, cap and overflow flag) restricted to the reviews whose bit is set in
+// `shown` (one bit per review), plus the masked pair total of every bitmap row from the same pass.  The mask stays on the device beside
+// the table (views share it) and is uploaded again only when `shown_gen` differs from the generation it went up under; order / grp
+// go up once per table.  pairs: [nc], idx: [nc][cap], n: [nc], ovf: [nc]
+void dev_audit_select(const DevTable* t, uint32_t nc, uint32_t n_reviews, const std::vector<uint32_t>& order, const std::vector<uint32_t>& grp,
+                      const std::vector<uint64_t>& shown, uint64_t shown_gen, uint32_t k, uint32_t cap,
+                      std::vector<uint32_t>* pairs, std::vector<uint32_t>* idx, std::vector<uint32_t>* n, std::vector<uint32_t>* ovf);
 // the violation bitmap [nc][n_tiles] of the table's most recent evaluation (device -> host copy)
 void dev_last_viol(const DevTable* t, uint32_t nc, std::vector<uint64_t>* viol);
 // ---- multi-GPU exchange step of a sharded sweep: one communicator per engine (= per GPU / rank)

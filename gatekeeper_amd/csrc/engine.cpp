@@ -22,6 +22,7 @@
 #include <sstream>
 
 #include "../../include/gkgpu.h"
+#include "audit_merge.hpp"
 #include "codegen.hpp"
 #include "device.hpp"
 #include "flatten.hpp"
@@ -321,6 +322,13 @@ struct gk_engine {
     std::vector<uint64_t> live;       // bit per slot: still the current version of a live object
     std::vector<uint64_t> shown;      // live AND NOT excluded from the audit process by the excluder generation `excl_gen`
     uint64_t excl_gen = 0;
+    uint64_t shown_gen = 0;           // moves whenever the contents of `shown` change (the device copy follows it: dev_audit_select)
+    // gk_resident_audit's autoreject side, kept while the evaluation (err_plan_gen) and the mask (err_shown_gen) stay as they are: per bitmap
+    // row the shown pairs whose Matcher.Match failed, and the slots of the first err_k of them in key order (+ the key ties of the last)
+    std::vector<uint64_t> err_pairs;
+    std::vector<std::vector<uint32_t>> err_slots;
+    uint64_t err_plan_gen = 0, err_shown_gen = 0;
+    uint32_t err_k = 0;
     gk_eval_out* ev = nullptr;        // bitmaps of the chunk's most recent evaluation
     uint64_t plan_gen = 0;            // ... and the plan generation they belong to
     uint64_t n_live = 0;
@@ -1748,21 +1756,26 @@ struct TopkHolder {
   std::vector<uint32_t> ids, counts, reviews, overflow;
 };
 
+// object-key order of the table, once: order = the reviews sorted by obj_key, grp = dense key rank with ties equal (what gk_table_topk
+// and gk_resident_audit hand to the device)
+static void table_key_order(gk_table* t) {
+  if (t->order.size() == t->n_reviews) return;
+  t->order.resize(t->n_reviews);
+  for (uint32_t i = 0; i < t->n_reviews; i++) t->order[i] = i;
+  // field-wise order == order of the \0-joined keys (\0 sorts below every byte a name can contain)
+  std::stable_sort(t->order.begin(), t->order.end(), [&](uint32_t a, uint32_t b) { return t->obj_key(a) < t->obj_key(b); });
+  t->grp.resize(t->n_reviews);
+  uint32_t gid = 0;
+  for (uint32_t p = 0; p < t->n_reviews; p++) {
+    if (p && t->obj_key(t->order[p]) != t->obj_key(t->order[p - 1])) gid++;
+    t->grp[p] = gid;
+  }
+}
+
 int gk_table_topk(gk_engine* e, gk_table* t, uint32_t k, gk_topk_out** out) {
   if (!e || !t || !out) return fail(GK_ERR_INVALID, "NULL argument");
   try {
-    if (t->order.size() != t->n_reviews) {   // object-key order of the table, once
-      t->order.resize(t->n_reviews);
-      for (uint32_t i = 0; i < t->n_reviews; i++) t->order[i] = i;
-      // field-wise order == order of the \0-joined keys (\0 sorts below every byte a name can contain)
-      std::stable_sort(t->order.begin(), t->order.end(), [&](uint32_t a, uint32_t b) { return t->obj_key(a) < t->obj_key(b); });
-      t->grp.resize(t->n_reviews);
-      uint32_t gid = 0;
-      for (uint32_t p = 0; p < t->n_reviews; p++) {
-        if (p && t->obj_key(t->order[p]) != t->obj_key(t->order[p - 1])) gid++;
-        t->grp[p] = gid;
-      }
-    }
+    table_key_order(t);
     std::unique_ptr<TopkHolder> h(new TopkHolder());
     const uint32_t cap = k + 64;
     h->ids = t->last_ids;
@@ -2547,88 +2560,143 @@ void resident_drop_chunk(gk_engine::ResChunk& c) {
 
 }  // namespace
 
+// What gk_resident_sweep and gk_resident_audit share (R.mu held by the caller): flatten what changed since the last sweep into a new
+// chunk (everything again when the set is compacted), evaluate the chunks whose bitmaps are stale, refresh the shown masks, and list
+// the constraint ids of the bitmap rows.  *t1: when flattening was done (sync_s / eval_s of gk_sweep_out).
+static int resident_update(gk_engine* e, uint64_t* flattened_out, std::chrono::steady_clock::time_point* t1_out, std::vector<uint32_t>* ids) {
+  gk_engine::Resident& R = e->resident;
+  ensure_plan(e);
+  uint64_t flattened = 0;
+  // compaction: when masked-out slots outnumber the live ones (or the chunks have piled up) everything is flattened
+  // again into one chunk
+  bool stale_rows = false;   // a constraint with dictionary predicates arrived: every chunk lacks its <leaf>.$d rows
+  for (auto& c : R.chunks) stale_rows = stale_rows || c.table->dict_gen != e->dict_reg.gen() || (c.table->pruned && c.table->reads_gen != e->dict_reg.reads_gen());
+  if (stale_rows || R.n_dead_slots > R.n_live + 1024 || R.chunks.size() > 16) {
+    for (auto& c : R.chunks) resident_drop_chunk(c);
+    R.chunks.clear();
+    R.pending.clear();
+    R.n_dead_slots = 0;
+    for (uint32_t id = 0; id < R.objs.size(); id++) if (R.objs[id].alive) { R.objs[id].chunk = UINT32_MAX; R.pending.push_back(id); }
+  }
+  if (!R.pending.empty()) {
+    std::vector<gk_review_in> ins;
+    gk_engine::ResChunk c;
+    for (uint32_t id : R.pending) {
+      if (!R.objs[id].alive) continue;
+      ins.push_back(resident_review_in(R, R.objs[id]));
+      c.obj_of_slot.push_back(id);
+    }
+    R.pending.clear();
+    if (!ins.empty()) {
+      std::vector<int32_t> st(ins.size(), GK_OK);
+      int rc = gk_table_create(e, ins.data(), ins.size(), GK_TABLE_RESIDENT | GK_TABLE_PRUNED, st.data(), &c.table);   // (stale chunks are flattened again: stale_rows above)
+      if (rc != GK_OK) return rc;
+      c.live.assign((ins.size() + 63) / 64, 0);
+      for (size_t k = 0; k < ins.size(); k++) {
+        gk_engine::ResObj& o = R.objs[c.obj_of_slot[k]];
+        o.chunk = (uint32_t)R.chunks.size(); o.slot = (uint32_t)k;
+        if (st[k] == GK_OK) { c.live[k / 64] |= 1ull << (k % 64); c.n_live++; }
+      }
+      flattened = ins.size();
+      R.flattened_total += flattened;
+      R.chunks.push_back(std::move(c));
+    }
+  }
+  *flattened_out = flattened;
+  *t1_out = std::chrono::steady_clock::now();
+  ensure_plan(e);   // flattening may have interned new key paths: the plan is re-bound to the dictionary first
+  uint64_t gen;
+  { std::shared_lock<std::shared_mutex> l(e->plan_rw); gen = e->plan_gen; }
+  for (auto& c : R.chunks) {
+    if (c.ev && c.plan_gen == gen) continue;   // bitmaps still valid: same rows, same policies
+    if (c.ev) { gk_eval_free(c.ev); c.ev = nullptr; }
+    int rc = gk_table_eval(e, c.table, 0, &c.ev);
+    if (rc != GK_OK) return rc;
+    c.plan_gen = gen;
+  }
+  {   // audit-process excluder over the resident objects (manager.go:599): a mask beside `live`, refreshed when the Config changes
+    std::shared_lock<std::shared_mutex> l(e->mu);
+    auto ex = e->excluder.find("audit");
+    for (auto& c : R.chunks) {
+      if (c.excl_gen == e->excluder_gen && c.shown.size() == c.live.size()) {
+        bool died = false;   // a slot was replaced or removed since the last sweep
+        for (size_t w = 0; w < c.live.size(); w++) { died = died || (c.shown[w] & ~c.live[w]); c.shown[w] &= c.live[w]; }
+        if (died) c.shown_gen++;
+        continue;
+      }
+      c.shown = c.live;
+      c.shown_gen++;
+      if (ex != e->excluder.end() && !ex->second.empty())
+        for (size_t k = 0; k < c.obj_of_slot.size(); k++) {
+          const gk_engine::ResObj& o = R.objs[c.obj_of_slot[k]];
+          if (excluder_matches(ex->second, o.is_namespace ? o.path.back() : o.ns)) c.shown[k / 64] &= ~(1ull << (k % 64));
+        }
+      c.excl_gen = e->excluder_gen;
+    }
+  }
+  // the constraint ids of the bitmap rows
+  if (!R.chunks.empty()) {
+    const gk_eval_out* ev0 = R.chunks[0].ev;
+    ids->assign(ev0->constraint_ids, ev0->constraint_ids + ev0->n_constraints);
+  } else {
+    { std::lock_guard<std::mutex> gate(e->plan_gate); }   // (a plan change that is waiting goes first)
+    std::shared_lock<std::shared_mutex> l(e->plan_rw);
+    *ids = e->plan_ids;
+    for (auto& g : e->extra) ids->insert(ids->end(), g->ids.begin(), g->ids.end());
+  }
+  return GK_OK;
+}
+
+// results, not pairs (pkg/audit/manager.go:902), over the shown slots of all chunks (R.mu held by the caller)
+static void resident_result_totals(gk_engine* e, const std::vector<uint32_t>& ids, std::vector<uint64_t>* results) {
+  gk_engine::Resident& R = e->resident;
+  const uint32_t nc = (uint32_t)ids.size();
+  // as gk_table_totals: the device says which violating live pairs can have more than one result; the others count one
+  std::shared_lock<std::shared_mutex> pl(e->plan_rw);
+  std::shared_lock<std::shared_mutex> l(e->mu);
+  for (auto& c : R.chunks) {
+    const gk_eval_out* ev = c.ev;
+    const uint32_t nt = ev->n_tiles, ncc = std::min<uint32_t>(ev->n_constraints, nc);
+    std::vector<uint64_t> shown_viol((size_t)nc * nt, 0);
+    for (uint32_t row = 0; row < ncc; row++)
+      for (uint32_t w = 0; w < nt; w++) shown_viol[(size_t)row * nt + w] = ev->viol[(size_t)row * nt + w] & c.shown[w];
+    std::vector<uint8_t> counted;
+    std::vector<uint64_t> counted_sum;
+    const std::vector<uint64_t> need = render_needed(e, c.table, ids, nt, shown_viol, &counted, &counted_sum);
+    for (uint32_t row = 0; row < ncc; row++) {
+      if (counted[row]) { (*results)[row] += counted_sum[row]; continue; }   // (round 4: counted on the device)
+      for (uint32_t w = 0; w < nt; w++) (*results)[row] += (uint64_t)__builtin_popcountll(shown_viol[(size_t)row * nt + w] & ~need[(size_t)row * nt + w]);
+    }
+    for (uint32_t slot = 0; slot < c.obj_of_slot.size(); slot++) {
+      const uint64_t bit = 1ull << (slot % 64);
+      bool any = false;
+      for (uint32_t row = 0; row < ncc && !any; row++) any = (need[(size_t)row * nt + slot / 64] & bit) != 0;
+      if (!any) continue;
+      const gk_review_in in = resident_review_in(R, R.objs[c.obj_of_slot[slot]]);
+      ReviewDoc doc = normalize_object(parse_json(in.json, in.json_len), parse_opt(in.namespace_json, in.namespace_len),
+                                       parse_opt(in.ns_object_json, in.ns_object_len), in.source, "", e->ns_cache);
+      for (uint32_t row = 0; row < ncc; row++) {
+        if (!(need[(size_t)row * nt + slot / 64] & bit)) continue;
+        const ConstraintRec& k = e->constraints[ids[row]];
+        auto it = e->templates.find(lower_str(k.kind));
+        if (it != e->templates.end()) (*results)[row] += it->second->render(doc.request, k.params, e->inventory).size();
+      }
+    }
+  }
+}
+
 int gk_resident_sweep(gk_engine* e, uint32_t flags, gk_sweep_out** out) {
   if (!e || !out) return fail(GK_ERR_INVALID, "NULL argument");
   try {
     gk_engine::Resident& R = e->resident;
     std::lock_guard<std::mutex> rl(R.mu);
     const auto t0 = std::chrono::steady_clock::now();
-    ensure_plan(e);
+    auto t1 = t0;
     uint64_t flattened = 0;
-    // compaction: when masked-out slots outnumber the live ones (or the chunks have piled up) everything is flattened
-    // again into one chunk
-    bool stale_rows = false;   // a constraint with dictionary predicates arrived: every chunk lacks its <leaf>.$d rows
-    for (auto& c : R.chunks) stale_rows = stale_rows || c.table->dict_gen != e->dict_reg.gen() || (c.table->pruned && c.table->reads_gen != e->dict_reg.reads_gen());
-    if (stale_rows || R.n_dead_slots > R.n_live + 1024 || R.chunks.size() > 16) {
-      for (auto& c : R.chunks) resident_drop_chunk(c);
-      R.chunks.clear();
-      R.pending.clear();
-      R.n_dead_slots = 0;
-      for (uint32_t id = 0; id < R.objs.size(); id++) if (R.objs[id].alive) { R.objs[id].chunk = UINT32_MAX; R.pending.push_back(id); }
-    }
-    if (!R.pending.empty()) {
-      std::vector<gk_review_in> ins;
-      gk_engine::ResChunk c;
-      for (uint32_t id : R.pending) {
-        if (!R.objs[id].alive) continue;
-        ins.push_back(resident_review_in(R, R.objs[id]));
-        c.obj_of_slot.push_back(id);
-      }
-      R.pending.clear();
-      if (!ins.empty()) {
-        std::vector<int32_t> st(ins.size(), GK_OK);
-        int rc = gk_table_create(e, ins.data(), ins.size(), GK_TABLE_RESIDENT | GK_TABLE_PRUNED, st.data(), &c.table);   // (stale chunks are flattened again: stale_rows above)
-        if (rc != GK_OK) return rc;
-        c.live.assign((ins.size() + 63) / 64, 0);
-        for (size_t k = 0; k < ins.size(); k++) {
-          gk_engine::ResObj& o = R.objs[c.obj_of_slot[k]];
-          o.chunk = (uint32_t)R.chunks.size(); o.slot = (uint32_t)k;
-          if (st[k] == GK_OK) { c.live[k / 64] |= 1ull << (k % 64); c.n_live++; }
-        }
-        flattened = ins.size();
-        R.flattened_total += flattened;
-        R.chunks.push_back(std::move(c));
-      }
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    ensure_plan(e);   // flattening may have interned new key paths: the plan is re-bound to the dictionary first
-    uint64_t gen;
-    { std::shared_lock<std::shared_mutex> l(e->plan_rw); gen = e->plan_gen; }
     std::unique_ptr<SweepHolder> h(new SweepHolder());
-    for (auto& c : R.chunks) {
-      if (c.ev && c.plan_gen == gen) continue;   // bitmaps still valid: same rows, same policies
-      if (c.ev) { gk_eval_free(c.ev); c.ev = nullptr; }
-      int rc = gk_table_eval(e, c.table, 0, &c.ev);
-      if (rc != GK_OK) return rc;
-      c.plan_gen = gen;
-    }
-    {   // audit-process excluder over the resident objects (manager.go:599): a mask beside `live`, refreshed when the Config changes
-      std::shared_lock<std::shared_mutex> l(e->mu);
-      auto ex = e->excluder.find("audit");
-      for (auto& c : R.chunks) {
-        if (c.excl_gen == e->excluder_gen && c.shown.size() == c.live.size()) {
-          for (size_t w = 0; w < c.live.size(); w++) c.shown[w] &= c.live[w];
-          continue;
-        }
-        c.shown = c.live;
-        if (ex != e->excluder.end() && !ex->second.empty())
-          for (size_t k = 0; k < c.obj_of_slot.size(); k++) {
-            const gk_engine::ResObj& o = R.objs[c.obj_of_slot[k]];
-            if (excluder_matches(ex->second, o.is_namespace ? o.path.back() : o.ns)) c.shown[k / 64] &= ~(1ull << (k % 64));
-          }
-        c.excl_gen = e->excluder_gen;
-      }
-    }
+    int rc = resident_update(e, &flattened, &t1, &h->ids);
+    if (rc != GK_OK) return rc;
     // per-constraint totals over the live, not excluded slots of all chunks
-    if (!R.chunks.empty()) {
-      const gk_eval_out* ev0 = R.chunks[0].ev;
-      h->ids.assign(ev0->constraint_ids, ev0->constraint_ids + ev0->n_constraints);
-    } else {
-      { std::lock_guard<std::mutex> gate(e->plan_gate); }   // (a plan change that is waiting goes first)
-      std::shared_lock<std::shared_mutex> l(e->plan_rw);
-      h->ids = e->plan_ids;
-      for (auto& g : e->extra) h->ids.insert(h->ids.end(), g->ids.begin(), g->ids.end());
-    }
     const uint32_t nc = (uint32_t)h->ids.size();
     h->pairs.assign(nc, 0); h->results.assign(nc, 0);
     uint64_t beyond = 0;
@@ -2638,40 +2706,7 @@ int gk_resident_sweep(gk_engine* e, uint32_t flags, gk_sweep_out** out) {
         for (uint32_t w = 0; w < ev->n_tiles; w++) h->pairs[row] += (uint64_t)__builtin_popcountll(ev->viol[(size_t)row * ev->n_tiles + w] & c.shown[w]);
       for (uint32_t w = 0; w < ev->n_tiles; w++) beyond += (uint64_t)__builtin_popcountll(ev->too_big[w] & c.shown[w]);
     }
-    if (flags & GK_SWEEP_RESULT_TOTALS) {   // results, not pairs (pkg/audit/manager.go:902)
-      // as gk_table_totals: the device says which violating live pairs can have more than one result; the others count one
-      std::shared_lock<std::shared_mutex> pl(e->plan_rw);
-      std::shared_lock<std::shared_mutex> l(e->mu);
-      for (auto& c : R.chunks) {
-        const gk_eval_out* ev = c.ev;
-        const uint32_t nt = ev->n_tiles, ncc = std::min<uint32_t>(ev->n_constraints, nc);
-        std::vector<uint64_t> shown_viol((size_t)nc * nt, 0);
-        for (uint32_t row = 0; row < ncc; row++)
-          for (uint32_t w = 0; w < nt; w++) shown_viol[(size_t)row * nt + w] = ev->viol[(size_t)row * nt + w] & c.shown[w];
-        std::vector<uint8_t> counted;
-        std::vector<uint64_t> counted_sum;
-        const std::vector<uint64_t> need = render_needed(e, c.table, h->ids, nt, shown_viol, &counted, &counted_sum);
-        for (uint32_t row = 0; row < ncc; row++) {
-          if (counted[row]) { h->results[row] += counted_sum[row]; continue; }   // (round 4: counted on the device)
-          for (uint32_t w = 0; w < nt; w++) h->results[row] += (uint64_t)__builtin_popcountll(shown_viol[(size_t)row * nt + w] & ~need[(size_t)row * nt + w]);
-        }
-        for (uint32_t slot = 0; slot < c.obj_of_slot.size(); slot++) {
-          const uint64_t bit = 1ull << (slot % 64);
-          bool any = false;
-          for (uint32_t row = 0; row < ncc && !any; row++) any = (need[(size_t)row * nt + slot / 64] & bit) != 0;
-          if (!any) continue;
-          const gk_review_in in = resident_review_in(R, R.objs[c.obj_of_slot[slot]]);
-          ReviewDoc doc = normalize_object(parse_json(in.json, in.json_len), parse_opt(in.namespace_json, in.namespace_len),
-                                           parse_opt(in.ns_object_json, in.ns_object_len), in.source, "", e->ns_cache);
-          for (uint32_t row = 0; row < ncc; row++) {
-            if (!(need[(size_t)row * nt + slot / 64] & bit)) continue;
-            const ConstraintRec& k = e->constraints[h->ids[row]];
-            auto it = e->templates.find(lower_str(k.kind));
-            if (it != e->templates.end()) h->results[row] += it->second->render(doc.request, k.params, e->inventory).size();
-          }
-        }
-      }
-    }
+    if (flags & GK_SWEEP_RESULT_TOTALS) resident_result_totals(e, h->ids, &h->results);
     R.swept = true;
     gk_sweep_out& p = h->pub;
     memset(&p, 0, sizeof p);
@@ -2686,6 +2721,147 @@ int gk_resident_sweep(gk_engine* e, uint32_t flags, gk_sweep_out** out) {
 }
 
 void gk_sweep_free(gk_sweep_out* o) { if (o) delete reinterpret_cast<SweepHolder*>(o); }
+
+namespace {
+struct AuditHolder {
+  gk_audit_out pub;   // first member
+  std::vector<uint32_t> ids, counts, objects, overflow;
+  std::vector<uint64_t> pairs, results, err_pairs;
+  std::vector<std::string> path_text;
+  std::vector<const char*> paths;
+};
+}  // namespace
+
+// What an audit run writes into a constraint's status, for the resident set (pkg/audit/manager.go:885-941 over auditFromCache's
+// objects): per chunk the device counts the shown violators of every bitmap row and picks the k with the smallest object key plus the
+// key ties of the k-th (dev_audit_select); the chunks' candidates are merged here (audit_merge.hpp) and only they are named to the caller.
+int gk_resident_audit(gk_engine* e, uint32_t k, uint32_t flags, gk_audit_out** out) {
+  if (!e || !out) return fail(GK_ERR_INVALID, "NULL argument");
+  try {
+    gk_engine::Resident& R = e->resident;
+    std::lock_guard<std::mutex> rl(R.mu);
+    std::unique_ptr<AuditHolder> h(new AuditHolder());
+    uint64_t flattened = 0;
+    auto t1 = std::chrono::steady_clock::now();
+    int rc = resident_update(e, &flattened, &t1, &h->ids);
+    if (rc != GK_OK) return rc;
+    const uint32_t nc = (uint32_t)h->ids.size();
+    const uint32_t stride = (uint32_t)std::min<uint64_t>(k, R.n_live) + 64;   // (k beyond the set's size selects everything)
+    h->pairs.assign(nc, 0); h->results.assign(nc, 0); h->err_pairs.assign(nc, 0); h->counts.assign(nc, 0); h->overflow.assign(nc, 0);
+    h->objects.assign((size_t)nc * stride, 0xFFFFFFFFu);
+    std::vector<std::vector<AuditCand>> cands(nc);
+    uint64_t beyond = 0;
+    for (auto& c : R.chunks) {
+      gk_table* t = c.table;
+      const gk_eval_out* ev = c.ev;
+      for (uint32_t w = 0; w < ev->n_tiles; w++) beyond += (uint64_t)__builtin_popcountll(ev->too_big[w] & c.shown[w]);
+      table_key_order(t);
+      const uint32_t kc = std::min(k, t->n_reviews), cap = kc + 64;
+      std::vector<uint32_t> pairs, idx, cnt, ovf;
+      {
+        std::shared_lock<std::shared_mutex> l(e->plan_rw);
+        if (e->plan_dirty || c.plan_gen != e->plan_gen) return fail(GK_ERR_DEVICE, "the policies changed while gk_resident_audit ran: call it again");
+        dev_audit_select(t->dev, (uint32_t)e->plan_ids.size(), t->n_reviews, t->order, t->grp, c.shown, c.shown_gen, kc, cap, &pairs, &idx, &cnt, &ovf);
+        for (size_t gi = 0; gi < e->extra.size() && gi < t->views.size(); gi++) {   // further plan groups: rows appended
+          std::vector<uint32_t> p, r, n, o;
+          dev_audit_select(t->views[gi], (uint32_t)e->extra[gi]->ids.size(), t->n_reviews, t->order, t->grp, c.shown, c.shown_gen, kc, cap, &p, &r, &n, &o);
+          pairs.insert(pairs.end(), p.begin(), p.end());
+          idx.insert(idx.end(), r.begin(), r.end());
+          cnt.insert(cnt.end(), n.begin(), n.end());
+          ovf.insert(ovf.end(), o.begin(), o.end());
+        }
+      }
+      const uint32_t rows = std::min<uint32_t>((uint32_t)pairs.size(), nc);
+      for (uint32_t row = 0; row < rows; row++) {
+        h->pairs[row] += pairs[row];
+        if (ovf[row]) h->overflow[row] = 1;
+        for (uint32_t i = 0; i < cnt[row]; i++) {
+          const uint32_t slot = idx[(size_t)row * cap + i];
+          if (slot < c.obj_of_slot.size()) cands[row].push_back(AuditCand{t->obj_key(slot), c.obj_of_slot[slot]});
+        }
+      }
+      // (violating pairs the host evaluation of over-limit reviews added are no part of the device bitmaps -- the kernels never set a
+      //  refused review's bit: where their slot is shown they join the candidates and the pairs, as in gk_table_topk)
+      std::vector<std::pair<uint32_t, uint32_t>> hv;
+      { std::lock_guard<std::mutex> hl(t->host_mu); if (t->host_ids == h->ids) hv = t->host_viol; }
+      for (auto& hp : hv) {
+        const uint32_t row = hp.first, slot = hp.second;
+        if (row >= rows || slot >= c.obj_of_slot.size() || !(c.shown[slot / 64] & (1ull << (slot % 64)))) continue;
+        h->pairs[row]++;
+        cands[row].push_back(AuditCand{t->obj_key(slot), c.obj_of_slot[slot]});
+      }
+      // Autoreject pairs (Matcher.Match returned an error: one Result each, which the audit counts and lists like any other) are rare and
+      // their bitmap is on the host already.  Counted once per (evaluation, mask); the rows that have any are then walked in key order
+      // until each has its k and their ties, or all it has -- once per (evaluation, mask, k) as well: where the first of them sits far
+      // down the key order the walk costs more than the two kernels (profiles/resident_audit.md).
+      if (c.err_shown_gen != c.shown_gen || c.err_plan_gen != c.plan_gen || c.err_pairs.size() != rows) {
+        c.err_pairs.assign(rows, 0);
+        for (uint32_t row = 0; row < rows; row++)
+          for (uint32_t w = 0; w < ev->n_tiles; w++) c.err_pairs[row] += (uint64_t)__builtin_popcountll(ev->err[(size_t)row * ev->n_tiles + w] & c.shown[w]);
+        c.err_shown_gen = c.shown_gen; c.err_plan_gen = c.plan_gen;
+        c.err_slots.clear();
+      }
+      if (c.err_slots.size() != rows || c.err_k != kc) {
+        c.err_slots.assign(rows, std::vector<uint32_t>());
+        c.err_k = kc;
+        struct ErrRow { uint32_t row; uint64_t left; uint32_t found = 0, grp_k = 0; };
+        std::vector<ErrRow> open;
+        for (uint32_t row = 0; row < rows; row++) if (kc && c.err_pairs[row]) open.push_back(ErrRow{row, c.err_pairs[row]});
+        for (uint32_t p = 0; p < t->n_reviews && !open.empty(); p++) {
+          const uint32_t slot = t->order[p];
+          if (!(c.shown[slot / 64] & (1ull << (slot % 64)))) continue;
+          for (size_t i = 0; i < open.size();) {
+            ErrRow& r = open[i];
+            bool close = false;
+            if ((ev->err[(size_t)r.row * ev->n_tiles + slot / 64] >> (slot % 64)) & 1ull) {
+              if (r.found >= kc && t->grp[p] != r.grp_k) close = true;
+              else {
+                if (r.found == kc - 1) r.grp_k = t->grp[p];
+                c.err_slots[r.row].push_back(slot);
+                r.found++;
+                close = --r.left == 0;
+              }
+            }
+            if (close) { open[i] = open.back(); open.pop_back(); } else i++;
+          }
+        }
+      }
+      for (uint32_t row = 0; row < rows; row++) {
+        h->err_pairs[row] += c.err_pairs[row];
+        for (uint32_t slot : c.err_slots[row]) cands[row].push_back(AuditCand{t->obj_key(slot), c.obj_of_slot[slot]});
+      }
+    }
+    std::unordered_map<uint32_t, uint32_t> path_of;   // resident object -> index into paths
+    for (uint32_t row = 0; row < nc; row++) {
+      if (!audit_merge(&cands[row], k, stride)) h->overflow[row] = 1;
+      h->counts[row] = (uint32_t)cands[row].size();
+      for (size_t i = 0; i < cands[row].size(); i++) {
+        auto ins = path_of.emplace(cands[row][i].obj, (uint32_t)h->path_text.size());
+        if (ins.second) {
+          std::string js = "[";
+          for (const std::string& seg : R.objs[cands[row][i].obj].path) { if (js.size() > 1) js += ","; json_escape(seg, js); }
+          h->path_text.push_back(js + "]");
+        }
+        h->objects[(size_t)row * stride + i] = ins.first->second;
+      }
+    }
+    for (const std::string& p : h->path_text) h->paths.push_back(p.c_str());
+    if (flags & GK_SWEEP_RESULT_TOTALS) resident_result_totals(e, h->ids, &h->results);
+    R.swept = true;
+    gk_audit_out& p = h->pub;
+    memset(&p, 0, sizeof p);
+    p.n_objects = R.n_live; p.n_constraints = nc; p.stride = stride; p.n_chunks = (uint32_t)R.chunks.size();
+    p.constraint_ids = h->ids.data(); p.pairs = h->pairs.data(); p.results = (flags & GK_SWEEP_RESULT_TOTALS) ? h->results.data() : nullptr;
+    p.counts = h->counts.data(); p.objects = h->objects.data(); p.overflow = h->overflow.data();
+    p.n_paths = (uint32_t)h->paths.size(); p.paths = h->paths.empty() ? nullptr : h->paths.data();
+    p.beyond_limits = beyond;
+    p.err_pairs = h->err_pairs.data();
+    *out = &h.release()->pub;
+    return GK_OK;
+  } catch (const std::exception& ex) { return fail(GK_ERR_DEVICE, ex.what()); }
+}
+
+void gk_audit_free(gk_audit_out* o) { if (o) delete reinterpret_cast<AuditHolder*>(o); }
 
 namespace {
 // the cached answer for one resident object, as gk_query's JSON; false: not resident / not swept / its slot is stale

@@ -764,6 +764,22 @@ class Driver:
         self.engine.lib.gk_sweep_free(out)
         return res
 
+    def ResidentAudit(self, k, result_totals=False):
+        """gk_resident_audit: the resident set brought up to date as by ResidentSweep, then per constraint the violating shown pairs and
+        the k violating objects with the smallest object key (key ties of the k-th included), selected on the device.  -> dict(n_objects,
+        n_chunks, beyond_limits, pairs {constraint id: n}, err_pairs {...} (match errors: autoreject), results {...} or None, lists {constraint id: ([inventory path], overflow)})"""
+        out = C.POINTER(L.gk_audit_out)()
+        self.engine._check(self.engine.lib.gk_resident_audit(self.engine.handle, int(k), L.GK_SWEEP_RESULT_TOTALS if result_totals else 0, C.byref(out)))
+        o = out.contents
+        paths = [tuple(json.loads(o.paths[i].decode())) for i in range(o.n_paths)]
+        ids = [int(o.constraint_ids[i]) for i in range(o.n_constraints)]
+        res = {"n_objects": int(o.n_objects), "n_chunks": int(o.n_chunks), "beyond_limits": int(o.beyond_limits),
+               "pairs": {cid: int(o.pairs[i]) for i, cid in enumerate(ids)}, "err_pairs": {cid: int(o.err_pairs[i]) for i, cid in enumerate(ids)},
+               "results": ({cid: int(o.results[i]) for i, cid in enumerate(ids)} if o.results else None),
+               "lists": {cid: ([paths[o.objects[i * o.stride + j]] for j in range(o.counts[i])], bool(o.overflow[i])) for i, cid in enumerate(ids)}}
+        self.engine.lib.gk_audit_free(out)
+        return res
+
     def ResidentReviewPreMatched(self, path, constraints):
         """gk_resident_review_ex(GK_QUERY_PRE_MATCHED): the violation sets of `constraints` (the caller matched them) for one resident
         object -- its resident text evaluated again through the admission batcher.  None when the object is not resident."""
@@ -929,6 +945,7 @@ class AuditReport(dict):
         super().__init__()
         self.totals_per_action = {}
         self.errors = []
+        self.n_rendered = None   # AuditReportFromCache: resident objects whose results were rendered (one ResidentReview each)
 
     def constraint_status(self, key, timestamp, violations_limit=20):
         """What updateConstraintStatus writes under the constraint's `status` (pkg/audit/manager.go:980-1034): auditTimestamp,
@@ -1043,6 +1060,53 @@ class Client:
                     res.append(Result(v["msg"], c, {} if v.get("autoreject") else v.get("details", {}), ea, scoped))
             out[path] = res
         return out, sweep
+
+    def AuditReportFromCache(self, limit=20, msg_size=256):
+        """What an audit run over the resident set writes into the constraints' status (pkg/audit/manager.go:885-941 behind auditFromCache):
+        AuditAggregate's report -- RESULT totals, totals per enforcement action, the `limit` smallest violations per constraint in
+        LimitQueue order -- from ONE gk_resident_audit.  Only the candidates the device selected are rendered (ResidentReview, once per
+        object); a constraint whose list overflowed on key ties falls back to every cached object.  -> AuditReport"""
+        audit = self.driver.ResidentAudit(limit, result_totals=True)
+        report = AuditReport()
+        if audit["beyond_limits"]:
+            report.errors.append(ReviewFailure(-1, "%d resident objects are beyond the engine's limits" % audit["beyond_limits"], LimitError("resident set")))
+        rendered = {}   # path -> rows of gk_query's JSON: one object may be a candidate of several constraints
+
+        def rows_of(path):
+            if path not in rendered:
+                try:
+                    rows = self.driver.ResidentReview(list(path))
+                except LimitError:
+                    rows = []   # (counted in beyond_limits)
+                if rows is None:
+                    raise EngineError(L.GK_ERR_INTERNAL, "audit candidate %r missing from the swept resident set" % (path,))
+                rendered[path] = rows
+            return rendered[path]
+
+        for cid, (c, ea, scoped) in self._active(AUDIT_EP).items():
+            if cid not in audit["pairs"]:
+                continue
+            paths, overflow = audit["lists"][cid]
+            if overflow:   # more key ties than the device list holds: every object, for this constraint only (exact, rare)
+                paths = list(self.cached)
+            cand = []
+            for path in paths:
+                obj = self.cached[path]
+                g, ver, k = obj_gvk(obj)
+                for v in rows_of(path):
+                    if v["constraint"] == cid:   # (an autoreject row is a result like any other: manager.go:885-941 lists what Review returned)
+                        cand.append({"group": g, "version": ver, "kind": k, "namespace": (obj.get("metadata") or {}).get("namespace", "") or "",
+                                     "name": (obj.get("metadata") or {}).get("name", "") or "", "message": truncate_string(v["msg"], msg_size),
+                                     "enforcementAction": ea, "enforcementActions": scoped})
+            cand.sort(key=lambda x: tuple(s_.encode("utf-8") for s_ in (x["group"], x["version"], x["kind"], x["namespace"], x["name"],
+                                                                       x["message"], x["enforcementAction"])))
+            key = (c.get("kind", ""), c.get("apiVersion", ""), (c.get("metadata") or {}).get("name", ""))
+            n_results, n_pairs = audit["results"][cid] + audit["err_pairs"][cid], audit["pairs"][cid] + audit["err_pairs"][cid]
+            report[key] = {"total": n_results, "total_pairs": n_pairs, "violations": cand[:limit]}
+            if n_results:
+                report.totals_per_action[ea] = report.totals_per_action.get(ea, 0) + n_results
+        report.n_rendered = len(rendered)
+        return report
 
     def _active(self, enforcement_point):
         """{engine constraint id: (constraint, enforcement action, scoped actions)} of the constraints enforced at this

@@ -357,6 +357,31 @@ typedef struct {
 #define GK_SWEEP_RESULT_TOTALS 1u
 int gk_resident_sweep(gk_engine* e, uint32_t flags, gk_sweep_out** out);
 void gk_sweep_free(gk_sweep_out* o);
+/* What an audit run writes into every constraint's status (pkg/audit/manager.go:112-203, 885-941) for the resident set, without a
+ * call per object: the set is brought up to date as by gk_resident_sweep; then, per chunk, the device counts the violating objects of
+ * every constraint among those an audit shows (live, not excluded from the audit process) and selects the `k` of them with the smallest
+ * object key -- ties on the k-th key included, as gk_table_topk does; the chunks' candidates are merged on the host.  objects[c] lists
+ * counts[c] indices into `paths`, ascending by object key: the caller renders only these (gk_resident_review) and breaks ties on
+ * the message.  Objects whose match FAILED for the constraint (autoreject results, which the audit counts and lists as well) are
+ * candidates in the same order and counted in err_pairs.  overflow[c] != 0: more key ties than `stride` (k + 64) holds -- review every object for that constraint.  k == 0: totals
+ * only.  `pairs` equals gk_resident_sweep's for the same state. */
+typedef struct {
+  uint64_t n_objects;               /* live objects */
+  uint32_t n_constraints, stride, n_chunks;
+  const uint32_t* constraint_ids;   /* [n_constraints] */
+  const uint64_t* pairs;            /* [n_constraints] violating shown (constraint, object) pairs */
+  const uint64_t* results;          /* only with GK_SWEEP_RESULT_TOTALS, as gk_sweep_out */
+  const uint32_t* counts;           /* [n_constraints] valid entries of objects[c] */
+  const uint32_t* objects;          /* [n_constraints][stride] indices into paths, ascending by object key */
+  const uint32_t* overflow;         /* [n_constraints] != 0: more key ties than stride holds */
+  uint32_t n_paths;
+  const char* const* paths;         /* [n_paths] JSON array of the object's inventory path segments */
+  uint64_t beyond_limits;
+  const uint64_t* err_pairs;        /* [n_constraints] shown pairs whose Matcher.Match returned an error (autoreject: one Result each, no part
+                                       of pairs / results); their objects are among objects[c] like the violating ones */
+} gk_audit_out;
+int gk_resident_audit(gk_engine* e, uint32_t k, uint32_t flags, gk_audit_out** out);
+void gk_audit_free(gk_audit_out* o);
 /* results of one swept object, in gk_query's JSON; GK_ERR_NOT_FOUND when the object is unknown or its answer is stale */
 int gk_resident_review(gk_engine* e, const char* const* path, size_t npath, char** results_json);
 /* the same for a caller that matched itself (gk_query_ex2's arguments).  With GK_QUERY_PRE_MATCHED the sweep's bitmaps -- match AND
