@@ -33,6 +33,7 @@ GK_REVIEW_EXCLUDED = 1
 GK_EVAL_WANT_MATCH, GK_EVAL_NO_DOWNLOAD, GK_EVAL_WANT_LIST, GK_EVAL_ASYNC, GK_EVAL_COLLECT, GK_EVAL_TIME_EACH, GK_EVAL_KERNEL_ONLY = 1, 2, 4, 8, 16, 32, 64
 GK_EVAL_DEVICE_ONLY = 128
 GK_SWEEP_RESULT_TOTALS = 1
+GK_VIOLATIONS_RENDER = 1
 
 EXPORTS = [
     "gk_engine_create", "gk_engine_destroy", "gk_last_error", "gk_version", "gk_template_add", "gk_template_remove",
@@ -40,6 +41,7 @@ EXPORTS = [
     "gk_table_eval", "gk_eval_free", "gk_render", "gk_render_error", "gk_free", "gk_dump", "gk_table_topk", "gk_topk_free",
     "gk_table_totals", "gk_totals_free", "gk_table_get_stats", "gk_batcher_start", "gk_batcher_stop", "gk_query", "gk_query_ex", "gk_query_ex2",
     "gk_resident_sweep", "gk_sweep_free", "gk_resident_review", "gk_resident_review_ex", "gk_resident_audit", "gk_audit_free",
+    "gk_resident_violations", "gk_violations_free",
     "gk_comm_unique_id", "gk_comm_init", "gk_comm_destroy", "gk_comm_info", "gk_table_sweep_sharded", "gk_shard_free",
     "gk_jit_quiesce", "gk_jit_cache_stats", "gk_jit_cache_dir", "gk_jit_cache_drop_memory", "gk_host_cpus", "gk_table_create_spool", "gk_spool_info_free", "gk_debug_set",
     # include/gksynth.h (bench / test plumbing)
@@ -105,6 +107,13 @@ class gk_audit_out(C.Structure):
                 ("constraint_ids", C.POINTER(C.c_uint32)), ("pairs", C.POINTER(C.c_uint64)), ("results", C.POINTER(C.c_uint64)),
                 ("counts", C.POINTER(C.c_uint32)), ("objects", C.POINTER(C.c_uint32)), ("overflow", C.POINTER(C.c_uint32)),
                 ("n_paths", C.c_uint32), ("paths", C.POINTER(C.c_char_p)), ("beyond_limits", C.c_uint64), ("err_pairs", C.POINTER(C.c_uint64))]
+
+
+class gk_violations_out(C.Structure):
+    _fields_ = [("n_objects", C.c_uint64), ("n_constraints", C.c_uint32), ("n_chunks", C.c_uint32), ("mask_words", C.c_uint32),
+                ("constraint_ids", C.POINTER(C.c_uint32)), ("total_objects", C.c_uint64), ("n_entries", C.c_uint32), ("paths", C.POINTER(C.c_char_p)),
+                ("viol", C.POINTER(C.c_uint64)), ("err", C.POINTER(C.c_uint64)), ("results_json", C.POINTER(C.c_char_p)),
+                ("beyond_limits", C.c_uint64), ("next_cursor", C.c_uint64)]
 
 
 class gk_shard_out(C.Structure):
@@ -233,6 +242,9 @@ def load(hostemu: bool | None = None):
     lib.gk_resident_audit.argtypes = [vp, u32, u32, C.POINTER(C.POINTER(gk_audit_out))]
     lib.gk_audit_free.argtypes = [C.POINTER(gk_audit_out)]
     lib.gk_audit_free.restype = None
+    lib.gk_resident_violations.argtypes = [vp, C.c_uint64, u32, u32, C.POINTER(C.POINTER(gk_violations_out))]
+    lib.gk_violations_free.argtypes = [C.POINTER(gk_violations_out)]
+    lib.gk_violations_free.restype = None
     lib.gk_batcher_start.argtypes = [vp, C.POINTER(gk_batch_opts)]
     lib.gk_batcher_stop.argtypes = [vp]
     lib.gk_batcher_stop.restype = None

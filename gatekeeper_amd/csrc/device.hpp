@@ -77,6 +77,16 @@ void dev_topk(const DevTable* t, uint32_t nc, const std::vector<uint32_t>& order
 void dev_audit_select(const DevTable* t, uint32_t nc, uint32_t n_reviews, const std::vector<uint32_t>& order, const std::vector<uint32_t>& grp,
                       const std::vector<uint64_t>& shown, uint64_t shown_gen, uint32_t k, uint32_t cap,
                       std::vector<uint32_t>* pairs, std::vector<uint32_t>* idx, std::vector<uint32_t>* n, std::vector<uint32_t>* ovf);
+// resident-set violation stream: every review that is set in `shown` and has a bit in at least one row of the most recent evaluation's
+// violation bitmap, with the rows it has them in.  dev_viol_index: cnt[w] = such reviews in bitmap word w (pw = ceil(n_reviews / 64)
+// words; `any`, when asked for, the reviews themselves as a bit word -- for a caller that merges further sources per word); it leaves
+// the prefix sum of cnt beside the table.  dev_viol_entries: the entries of the words [w0, w1) -- reviews ascending, masks
+// [entries][ceil(nc / 64)], bit r = row r -- placed by that prefix sum; it throws when the index belongs to another evaluation or mask.
+// The mask is dev_audit_select's device copy (same shown_gen rule).
+void dev_viol_index(const DevTable* t, uint32_t nc, uint32_t n_reviews, const std::vector<uint64_t>& shown, uint64_t shown_gen,
+                    std::vector<uint32_t>* cnt, std::vector<uint64_t>* any = nullptr);
+void dev_viol_entries(const DevTable* t, uint32_t nc, uint32_t n_reviews, const std::vector<uint64_t>& shown, uint64_t shown_gen, uint32_t w0, uint32_t w1,
+                      std::vector<uint32_t>* reviews, std::vector<uint64_t>* masks);
 // the violation bitmap [nc][n_tiles] of the table's most recent evaluation (device -> host copy)
 void dev_last_viol(const DevTable* t, uint32_t nc, std::vector<uint64_t>* viol);
 // ---- multi-GPU exchange step of a sharded sweep: one communicator per engine (= per GPU / rank)

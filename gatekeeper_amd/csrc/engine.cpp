@@ -29,6 +29,7 @@
 #include "lower.hpp"
 #include "pe.hpp"
 #include "regex.hpp"
+#include "viol_stream.hpp"
 
 using namespace gk;
 
@@ -329,6 +330,12 @@ struct gk_engine {
     std::vector<std::vector<uint32_t>> err_slots;
     uint64_t err_plan_gen = 0, err_shown_gen = 0;
     uint32_t err_k = 0;
+    // gk_resident_violations' index, kept like the err_* fields while the evaluation (vs_plan_gen) and the mask (vs_shown_gen) stand:
+    // vs_prefix = exclusive prefix sum of the entries per bitmap word over ALL sources (device bits of every plan group, autoreject
+    // bits, host-evaluated violations); vs_extra = the shown slots that have an autoreject bit or a host-evaluated violation, ascending
+    std::vector<uint64_t> vs_prefix;
+    std::vector<uint32_t> vs_extra;
+    uint64_t vs_plan_gen = 0, vs_shown_gen = 0;
     gk_eval_out* ev = nullptr;        // bitmaps of the chunk's most recent evaluation
     uint64_t plan_gen = 0;            // ... and the plan generation they belong to
     uint64_t n_live = 0;
@@ -343,6 +350,11 @@ struct gk_engine {
     std::vector<ResChunk> chunks;
     bool swept = false;               // bitmaps are current (no put / remove / policy change since the last sweep)
     uint64_t n_live = 0, n_dead_slots = 0, flattened_total = 0;
+    // gk_resident_violations: set_gen moves with every put / remove that changes the set, compactions with every time the chunks are
+    // flattened again; vs_* is the state the stream generation vs_gen (0: no stream yet) was handed out for
+    uint64_t set_gen = 0, compactions = 0;
+    uint32_t vs_gen = 0;
+    uint64_t vs_set_gen = 0, vs_compactions = 0, vs_plan_gen = 0, vs_excl_gen = 0;
   } resident;
   // ---- admission micro-batcher (gk_query): concurrent single-review calls coalesced into one table + one launch
   struct BatchResult;   // one evaluated batch: table + bitmaps, shared by its requests until the last one has rendered
@@ -1135,6 +1147,7 @@ int gk_data_put(gk_engine* e, const char* const* path, size_t npath, const char*
     // a Namespace object is part of the review of every object living in it (Matchable.Namespace, namespaceObject)
     if (is_ns) { auto bn = R.by_ns.find(p[3]); if (bn != R.by_ns.end()) for (uint32_t d : bn->second) resident_requeue(R, d); }
     R.swept = false;
+    R.set_gen++;
     return GK_OK;
   } catch (const JsonError& ex) { return fail(GK_ERR_INVALID, ex.what()); }
 }
@@ -1167,6 +1180,7 @@ int gk_data_remove(gk_engine* e, const char* const* path, size_t npath) {
     R.n_live--;
     if (is_ns) { auto bn = R.by_ns.find(p[3]); if (bn != R.by_ns.end()) for (uint32_t d : bn->second) resident_requeue(R, d); }
     R.swept = false;
+    R.set_gen++;
   }
   return GK_OK;
 }
@@ -2576,6 +2590,7 @@ static int resident_update(gk_engine* e, uint64_t* flattened_out, std::chrono::s
     R.chunks.clear();
     R.pending.clear();
     R.n_dead_slots = 0;
+    R.compactions++;
     for (uint32_t id = 0; id < R.objs.size(); id++) if (R.objs[id].alive) { R.objs[id].chunk = UINT32_MAX; R.pending.push_back(id); }
   }
   if (!R.pending.empty()) {
@@ -2885,6 +2900,250 @@ bool resident_answer(gk_engine* e, uint32_t id, std::string* json, int* status, 
   return true;
 }
 }  // namespace
+
+// ---- gk_resident_violations: every shown resident object with at least one result, in pages (viol_stream.hpp holds the pure part)
+namespace {
+struct ViolationsHolder {
+  gk_violations_out pub;   // first member
+  std::vector<uint32_t> ids;
+  std::vector<uint64_t> viol, err;
+  std::string path_arena;   // the page's path texts, \0 between them: one allocation (a string per entry was most of a 65 536-entry page's time)
+  std::vector<std::string> result_text;
+  std::vector<const char*> paths, results;
+};
+const char* const k_stream_moved = "the resident set or the policies changed since the stream began: start again with cursor 0";
+
+// the plan groups of a chunk as the device sees them: (table or view, rows, first row among all constraints).  plan_rw held shared.
+struct ViolGroup { const DevTable* dev; uint32_t nc, row0; };
+std::vector<ViolGroup> viol_groups(gk_engine* e, gk_table* t) {
+  std::vector<ViolGroup> g;
+  uint32_t row0 = (uint32_t)e->plan_ids.size();
+  g.push_back(ViolGroup{t->dev, row0, 0});
+  for (size_t gi = 0; gi < e->extra.size() && gi < t->views.size(); gi++) {
+    g.push_back(ViolGroup{t->views[gi], (uint32_t)e->extra[gi]->ids.size(), row0});
+    row0 += (uint32_t)e->extra[gi]->ids.size();
+  }
+  return g;
+}
+
+// The index of one chunk: per plan group the device counts the shown reviews with a bit per bitmap word (dev_viol_index) and keeps the
+// prefix sum that places its entries.  Where nothing else can add an entry -- one group, no autoreject bit, no host-evaluated
+// violation: the common state -- those counts ARE the index and 4 bytes per word come back.  Otherwise an object may be named by
+// several sources, so the groups' `any` words come back as well and are ORed here with the host's.  R.mu and plan_rw (shared) held.
+void resident_viol_index(gk_engine* e, gk_engine::ResChunk& c, const std::vector<uint32_t>& ids) {
+  gk_table* t = c.table;
+  const gk_eval_out* ev = c.ev;
+  const uint32_t pw = (t->n_reviews + 63u) / 64u, nt = ev->n_tiles, rows = std::min<uint32_t>(ev->n_constraints, (uint32_t)ids.size());
+  std::vector<uint64_t> extra(pw, 0);
+  for (uint32_t row = 0; row < rows; row++)
+    for (uint32_t w = 0; w < pw && w < nt; w++) extra[w] |= ev->err[(size_t)row * nt + w];
+  {
+    std::lock_guard<std::mutex> hl(t->host_mu);
+    if (t->host_ids == ids)
+      for (auto& hp : t->host_viol) if (hp.first < rows && hp.second < t->n_reviews) extra[hp.second / 64] |= 1ull << (hp.second % 64);
+  }
+  bool has_extra = false;
+  for (uint32_t w = 0; w < pw; w++) { extra[w] &= w < c.shown.size() ? c.shown[w] : 0ull; has_extra = has_extra || extra[w]; }
+  const std::vector<ViolGroup> groups = viol_groups(e, t);
+  const bool merged = has_extra || groups.size() > 1;
+  std::vector<uint64_t> any(pw, 0), a;
+  std::vector<uint32_t> cnt(pw, 0), n;
+  for (const ViolGroup& g : groups) {
+    if (g.nc == 0) continue;
+    dev_viol_index(g.dev, g.nc, t->n_reviews, c.shown, c.shown_gen, &n, merged ? &a : nullptr);
+    if (n.size() != pw || (merged && a.size() != pw)) throw std::runtime_error("dev_viol_index: wrong size");
+    if (merged) for (uint32_t w = 0; w < pw; w++) any[w] |= a[w];
+    else cnt = n;
+  }
+  c.vs_prefix.assign((size_t)pw + 1, 0);
+  for (uint32_t w = 0; w < pw; w++) c.vs_prefix[w + 1] = c.vs_prefix[w] + (merged ? (uint64_t)__builtin_popcountll(any[w] | extra[w]) : cnt[w]);
+  c.vs_extra.clear();
+  for (uint32_t w = 0; w < pw; w++)
+    for (uint64_t m = extra[w]; m; m &= m - 1) c.vs_extra.push_back(w * 64u + (uint32_t)__builtin_ctzll(m));
+  c.vs_plan_gen = c.plan_gen; c.vs_shown_gen = c.shown_gen;
+}
+}  // namespace
+
+int gk_resident_violations(gk_engine* e, uint64_t cursor, uint32_t max_objects, uint32_t flags, gk_violations_out** out) {
+  if (!e || !out) return fail(GK_ERR_INVALID, "NULL argument");
+  try {
+    gk_engine::Resident& R = e->resident;
+    std::lock_guard<std::mutex> rl(R.mu);
+    std::unique_ptr<ViolationsHolder> h(new ViolationsHolder());
+    if (cursor == 0) {   // a stream begins: the set is brought up to date as by gk_resident_sweep
+      uint64_t flattened = 0;
+      auto t1 = std::chrono::steady_clock::now();
+      int rc = resident_update(e, &flattened, &t1, &h->ids);
+      if (rc != GK_OK) return rc;
+      R.swept = true;
+    } else {
+      // nothing is flattened or evaluated for a later page: whatever the answer depends on must stand as the stream's first call left it
+      if (!R.swept || R.vs_gen == 0 || R.set_gen != R.vs_set_gen || R.compactions != R.vs_compactions) return fail(GK_ERR_INVALID, k_stream_moved);
+      { std::shared_lock<std::shared_mutex> l(e->mu); if (e->excluder_gen != R.vs_excl_gen) return fail(GK_ERR_INVALID, k_stream_moved); }
+      if (!R.chunks.empty()) h->ids.assign(R.chunks[0].ev->constraint_ids, R.chunks[0].ev->constraint_ids + R.chunks[0].ev->n_constraints);
+    }
+    const uint32_t nc = (uint32_t)h->ids.size(), mw = (nc + 63u) / 64u;
+    uint64_t beyond = 0, total = 0;
+    std::vector<uint32_t> slots;
+    uint32_t page_chunk = 0;
+    uint64_t next_cursor = 0;
+    {
+      std::shared_lock<std::shared_mutex> pl(e->plan_rw);
+      if (cursor == 0) {
+        for (auto& c : R.chunks) {
+          if (e->plan_dirty || c.plan_gen != e->plan_gen) return fail(GK_ERR_DEVICE, "the policies changed while gk_resident_violations ran: call it again");
+          if (c.vs_prefix.empty() || c.vs_plan_gen != c.plan_gen || c.vs_shown_gen != c.shown_gen) resident_viol_index(e, c, h->ids);
+        }
+        const uint64_t plan_gen = e->plan_gen, excl_gen = R.chunks.empty() ? 0 : R.chunks[0].excl_gen;
+        if (R.vs_gen == 0 || R.vs_set_gen != R.set_gen || R.vs_compactions != R.compactions || R.vs_plan_gen != plan_gen || R.vs_excl_gen != excl_gen) {
+          R.vs_gen = viol_next_gen(R.vs_gen);
+          R.vs_set_gen = R.set_gen; R.vs_compactions = R.compactions; R.vs_plan_gen = plan_gen; R.vs_excl_gen = excl_gen;
+        }
+      } else {
+        if (e->plan_dirty || e->plan_gen != R.vs_plan_gen) return fail(GK_ERR_INVALID, k_stream_moved);
+        for (auto& c : R.chunks)
+          if (!c.ev || c.plan_gen != e->plan_gen || c.vs_prefix.empty() || c.vs_plan_gen != c.plan_gen || c.vs_shown_gen != c.shown_gen || c.excl_gen != R.vs_excl_gen)
+            return fail(GK_ERR_INVALID, k_stream_moved);
+      }
+      std::vector<uint32_t> chunk_words;
+      for (auto& c : R.chunks) {
+        chunk_words.push_back((uint32_t)(c.vs_prefix.size() - 1));
+        total += c.vs_prefix.back();
+        const gk_eval_out* ev = c.ev;
+        for (uint32_t w = 0; w < ev->n_tiles && w < c.shown.size(); w++) beyond += (uint64_t)__builtin_popcountll(ev->too_big[w] & c.shown[w]);
+      }
+      // where the page begins: the cursor's word, or the first word of the set that has entries
+      ViolCursor at;
+      bool have = false;
+      if (cursor != 0) {
+        if (!viol_cursor_check(cursor, R.vs_gen, chunk_words, &at)) return fail(GK_ERR_INVALID, k_stream_moved);
+        if (viol_next_word(R.chunks[at.chunk].vs_prefix, at.word) != at.word) return fail(GK_ERR_INVALID, k_stream_moved);   // (no page begins at a word without entries)
+        have = true;
+      } else {
+        at.gen = R.vs_gen;
+        for (uint32_t ci = 0; ci < R.chunks.size() && !have; ci++) {
+          const uint32_t w = viol_next_word(R.chunks[ci].vs_prefix, 0);
+          if (w < chunk_words[ci]) { at.chunk = ci; at.word = w; have = true; }
+        }
+      }
+      if (have) {
+        gk_engine::ResChunk& c = R.chunks[at.chunk];
+        gk_table* t = c.table;
+        const gk_eval_out* ev = c.ev;
+        const uint32_t w0 = at.word, w1 = viol_page_end(c.vs_prefix, w0, max_objects);
+        const uint32_t nt = ev->n_tiles, rows = std::min<uint32_t>(ev->n_constraints, nc);
+        page_chunk = at.chunk;
+        // the device's entries of every plan group, then the slots only the host knows
+        const std::vector<ViolGroup> groups = viol_groups(e, t);
+        std::vector<std::vector<uint32_t>> rev(groups.size());
+        std::vector<std::vector<uint64_t>> msk(groups.size());
+        for (size_t gi = 0; gi < groups.size(); gi++) {
+          if (groups[gi].nc == 0) continue;
+          dev_viol_entries(groups[gi].dev, groups[gi].nc, t->n_reviews, c.shown, c.shown_gen, w0, w1, &rev[gi], &msk[gi]);
+          slots = slots.empty() ? rev[gi] : viol_merge_slots(slots, rev[gi]);
+        }
+        const auto x0 = std::lower_bound(c.vs_extra.begin(), c.vs_extra.end(), w0 * 64u);
+        const auto x1 = std::lower_bound(x0, c.vs_extra.end(), (uint64_t)w1 * 64u, [](uint32_t s, uint64_t lim) { return s < lim; });
+        const std::vector<uint32_t> extra(x0, x1);
+        if (!extra.empty()) slots = viol_merge_slots(slots, extra);
+        if (slots.size() != c.vs_prefix[w1] - c.vs_prefix[w0]) throw std::runtime_error("gk_resident_violations: the page's entries do not add up to the chunk's index");
+        h->viol.assign(slots.size() * (size_t)mw, 0); h->err.assign(slots.size() * (size_t)mw, 0);
+        for (size_t gi = 0; gi < groups.size(); gi++)
+          if (groups[gi].nc && !viol_scatter(slots, mw, rev[gi], msk[gi], groups[gi].nc, groups[gi].row0, &h->viol))
+            throw std::runtime_error("gk_resident_violations: a plan group's entries do not fit the page");
+        for (uint32_t slot : extra) {   // autoreject pairs: the downloaded error bitmap
+          const size_t i = viol_find(slots, slot);
+          for (uint32_t row = 0; row < rows; row++)
+            if ((ev->err[(size_t)row * nt + slot / 64] >> (slot % 64)) & 1ull) h->err[i * mw + row / 64] |= 1ull << (row % 64);
+        }
+        {   // violating pairs the host evaluation of over-limit reviews added: no part of the device bitmaps (as gk_resident_audit)
+          std::lock_guard<std::mutex> hl(t->host_mu);
+          if (t->host_ids == h->ids)
+            for (auto& hp : t->host_viol) {
+              if (hp.first >= rows || hp.second / 64 < w0 || hp.second / 64 >= w1) continue;
+              const size_t i = viol_find(slots, hp.second);
+              if (i < slots.size()) h->viol[i * mw + hp.first / 64] |= 1ull << (hp.first % 64);   // (not on the page: not shown)
+            }
+        }
+        // the next page begins at the next word with entries, in this chunk or a later one
+        ViolCursor nx;
+        nx.gen = R.vs_gen;
+        bool more = false;
+        for (uint32_t ci = at.chunk; ci < R.chunks.size() && !more; ci++) {
+          const uint32_t w = viol_next_word(R.chunks[ci].vs_prefix, ci == at.chunk ? w1 : 0);
+          if (w < chunk_words[ci]) { nx.chunk = ci; nx.word = w; more = true; }
+        }
+        if (more) {
+          next_cursor = viol_cursor_pack(nx);
+          if (!next_cursor) throw std::runtime_error("gk_resident_violations: the position does not fit a cursor");
+        }
+      }
+    }
+    // ---- the page's objects: inventory paths, and with GK_VIOLATIONS_RENDER what gk_resident_review answers for each
+    const gk_engine::ResChunk* pc = slots.empty() ? nullptr : &R.chunks[page_chunk];
+    {
+      size_t room = 0;
+      for (uint32_t slot : slots) { room += 3; for (const std::string& seg : R.objs[pc->obj_of_slot[slot]].path) room += seg.size() + 3; }
+      std::string& a = h->path_arena;
+      a.reserve(room + room / 8);   // (escapes are rare; the string grows by itself when they are not)
+      std::vector<size_t> at;
+      at.reserve(slots.size());
+      for (uint32_t slot : slots) {
+        at.push_back(a.size());
+        a += '[';
+        bool first = true;
+        for (const std::string& seg : R.objs[pc->obj_of_slot[slot]].path) { if (!first) a += ','; first = false; json_escape(seg, a); }
+        a += ']';
+        a += '\0';
+      }
+      h->paths.reserve(slots.size());
+      for (size_t off : at) h->paths.push_back(a.data() + off);   // (after the last append: the arena no longer moves)
+    }
+    if ((flags & GK_VIOLATIONS_RENDER) && !slots.empty()) {
+      h->result_text.resize(slots.size());
+      size_t n_threads = std::max<size_t>(1, std::min<size_t>(host_cpus(), slots.size()));
+      if (const char* ht = getenv("GK_HOST_THREADS")) n_threads = std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, atoi(ht)), slots.size()));
+      std::atomic<size_t> next{0};
+      std::mutex err_mu;
+      std::string first_err;
+      int first_status = GK_OK;
+      auto worker = [&](size_t) {   // one object per task, handed out in page order
+        for (;;) {
+          const size_t i = next.fetch_add(1);
+          if (i >= slots.size()) return;
+          std::string err;
+          int st = GK_OK;
+          try {
+            if (!resident_answer(e, pc->obj_of_slot[slots[i]], &h->result_text[i], &st, &err, true)) { st = GK_ERR_INVALID; err = k_stream_moved; }
+          } catch (const std::exception& ex) { st = GK_ERR_REGO; err = ex.what(); }
+          if (st != GK_OK) {
+            std::lock_guard<std::mutex> l(err_mu);
+            if (first_status == GK_OK) { first_status = st; first_err = err; }
+            next.store(slots.size());   // (the call fails: the remaining objects are not rendered)
+          }
+        }
+      };
+      HostWorkers::get().run(n_threads, worker);
+      if (first_status != GK_OK) return fail(first_status, first_err);
+      for (const std::string& r : h->result_text) h->results.push_back(r.c_str());
+    }
+    gk_violations_out& p = h->pub;
+    memset(&p, 0, sizeof p);
+    p.n_objects = R.n_live; p.n_constraints = nc; p.n_chunks = (uint32_t)R.chunks.size(); p.mask_words = mw;
+    p.constraint_ids = h->ids.data();
+    p.total_objects = total;
+    p.n_entries = (uint32_t)slots.size();
+    p.paths = h->paths.empty() ? nullptr : h->paths.data();
+    p.viol = h->viol.data(); p.err = h->err.data();
+    p.results_json = h->results.empty() ? nullptr : h->results.data();
+    p.beyond_limits = beyond;
+    p.next_cursor = next_cursor;
+    *out = &h.release()->pub;
+    return GK_OK;
+  } catch (const std::exception& ex) { return fail(GK_ERR_DEVICE, ex.what()); }
+}
+
+void gk_violations_free(gk_violations_out* o) { if (o) delete reinterpret_cast<ViolationsHolder*>(o); }
 
 // Driver.Query's `constraints` as a sorted id list; GK_ERR_NOT_FOUND for an id that is not loaded
 static int wanted_ids(gk_engine* e, const uint32_t* ids, size_t n, std::vector<uint32_t>* out) {

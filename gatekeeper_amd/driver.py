@@ -780,6 +780,38 @@ class Driver:
         self.engine.lib.gk_audit_free(out)
         return res
 
+    def ResidentViolations(self, max_objects=4096, render=True):
+        """gk_resident_violations as a generator over its pages: every shown resident object with at least one result, chunk by chunk in
+        slot order.  Yields (inventory path tuple, [violated constraint ids], [autoreject constraint ids], rows of gk_query's JSON -- what
+        ResidentReview returns -- or None without `render`) per entry and frees each page.  The first call brings the set up to date; a
+        put / remove or a policy change while the generator is open makes its next page fail (EngineError, GK_ERR_INVALID)."""
+        lib, cursor = self.engine.lib, 0
+        while True:
+            out = C.POINTER(L.gk_violations_out)()
+            self.engine._check(lib.gk_resident_violations(self.engine.handle, cursor, int(max_objects), L.GK_VIOLATIONS_RENDER if render else 0, C.byref(out)))
+            try:
+                o = out.contents
+                ids, mw = [int(o.constraint_ids[i]) for i in range(o.n_constraints)], int(o.mask_words)
+                page = []
+                for i in range(o.n_entries):
+                    sets = []
+                    for arr in (o.viol, o.err):
+                        got = []
+                        for w in range(mw):
+                            m = int(arr[i * mw + w])
+                            while m:
+                                low = m & -m
+                                got.append(ids[w * 64 + low.bit_length() - 1])
+                                m ^= low
+                        sets.append(got)
+                    page.append((tuple(json.loads(o.paths[i].decode())), sets[0], sets[1], json.loads(o.results_json[i].decode()) if render else None))
+                cursor = int(o.next_cursor)
+            finally:
+                lib.gk_violations_free(out)
+            yield from page
+            if not cursor:
+                return
+
     def ResidentReviewPreMatched(self, path, constraints):
         """gk_resident_review_ex(GK_QUERY_PRE_MATCHED): the violation sets of `constraints` (the caller matched them) for one resident
         object -- its resident text evaluated again through the admission batcher.  None when the object is not resident."""
@@ -1060,6 +1092,47 @@ class Client:
                     res.append(Result(v["msg"], c, {} if v.get("autoreject") else v.get("details", {}), ea, scoped))
             out[path] = res
         return out, sweep
+
+    def AuditStreamFromCache(self, page=4096):
+        """AuditFromCache for a caller that acts on every single result (manager.go:927-939: logViolation, Publish, emitEvent): a generator
+        of (path tuple, [Result]) over the cached objects that HAVE results at the audit enforcement point, from gk_resident_violations --
+        no call per cached object, nothing rendered for an object without results.  The Results are built as AuditFromCache builds them."""
+        info = self._active(AUDIT_EP)
+        for path, _viol, _err, rows in self.driver.ResidentViolations(page, render=True):
+            res = []
+            for v in rows:
+                if v["constraint"] in info:
+                    c, ea, scoped = info[v["constraint"]]
+                    res.append(Result(v["msg"], c, {} if v.get("autoreject") else v.get("details", {}), ea, scoped))
+            if res:
+                yield path, res
+
+    def AuditViolationMessages(self, timestamp, page=4096, msg_size=256):
+        """What an audit run publishes per result: one dict per Result of the resident set in violationMsg's shape (manager.go:1188-1212;
+        keys are ExportMsg's json tags, pkg/export/util/util.go:72-90, and what `omitempty` drops -- empty strings, maps and lists -- is left
+        out).  `details` is there exactly when the result row carries a `details` member; autoreject rows get none (how the stock driver
+        fills Metadata["details"] for them is unpinned: DESIGN.md section 2)."""
+        info = self._active(AUDIT_EP)
+        for path, _viol, _err, rows in self.driver.ResidentViolations(page, render=True):
+            obj = self.cached[path]
+            g, ver, kind = obj_gvk(obj)
+            md = obj.get("metadata") or {}
+            for v in rows:
+                if v["constraint"] not in info:
+                    continue
+                c, ea, scoped = info[v["constraint"]]
+                cg, cver, ckind = obj_gvk(c)
+                cmd = c.get("metadata") or {}
+                ann = {k: a for k, a in (cmd.get("annotations") or {}).items() if k != "kubectl.kubernetes.io/last-applied-configuration"}
+                msg = {"id": timestamp, "eventType": "violation_audited", "group": cg, "version": cver, "kind": ckind, "name": cmd.get("name", "") or "",
+                       "namespace": cmd.get("namespace", "") or "", "message": truncate_string(v["msg"], msg_size), "enforcementAction": ea,
+                       "enforcementActions": list(scoped or ()), "constraintAnnotations": ann, "resourceGroup": g, "resourceAPIVersion": ver,
+                       "resourceKind": kind, "resourceNamespace": md.get("namespace", "") or "", "resourceName": md.get("name", "") or "",
+                       "resourceLabels": dict(md.get("labels") or {})}
+                msg = {k: x for k, x in msg.items() if x not in ("", {}, [])}
+                if "details" in v and not v.get("autoreject"):
+                    msg["details"] = v["details"]
+                yield msg
 
     def AuditReportFromCache(self, limit=20, msg_size=256):
         """What an audit run over the resident set writes into the constraints' status (pkg/audit/manager.go:885-941 behind auditFromCache):

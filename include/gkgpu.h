@@ -382,6 +382,33 @@ typedef struct {
 } gk_audit_out;
 int gk_resident_audit(gk_engine* e, uint32_t k, uint32_t flags, gk_audit_out** out);
 void gk_audit_free(gk_audit_out* o);
+/* The other half of what an audit run does with auditFromCache's results (pkg/audit/manager.go:927-939): for every single result it
+ * calls logViolation, exportSystem.Publish(violationMsg(...)) and, when asked, emitEvent.  gk_resident_violations names every shown
+ * resident object that has at least one result, with the constraints it has them for, without a call per cached object: per chunk the
+ * device compacts the bitmaps of the last sweep into (object, constraint mask) entries; autoreject pairs and pairs the host evaluator
+ * completed are merged in on the host.  The stream comes in pages: chunk by chunk, slot order within a chunk; a page is the longest
+ * run of whole 64-slot bitmap words of one chunk whose entries fit in max_objects (below 64 counts as 64), never spans chunks, and may
+ * therefore hold fewer entries than max_objects.  cursor 0 begins a stream: the set is brought up to date as by gk_resident_sweep.
+ * next_cursor continues it without flattening or evaluating anything; it is opaque, and when a put or remove, a policy change, a new
+ * process excluder or a compaction of the set came between, the call fails with GK_ERR_INVALID ("... start again with cursor 0") rather
+ * than answer from stale bitmaps.  Bit r of a mask (word r / 64, bit r % 64) is constraint_ids[r].  With GK_VIOLATIONS_RENDER,
+ * results_json[i] is byte for byte what gk_resident_review returns for paths[i]; rendering runs on the host workers (GK_HOST_THREADS). */
+#define GK_VIOLATIONS_RENDER 1u
+typedef struct {
+  uint64_t n_objects;               /* live objects */
+  uint32_t n_constraints, n_chunks, mask_words;   /* mask_words = ceil(n_constraints / 64) */
+  const uint32_t* constraint_ids;   /* [n_constraints], bitmap-row order: bit r of a mask = constraint_ids[r] */
+  uint64_t total_objects;           /* entries of the WHOLE stream (all pages) */
+  uint32_t n_entries;               /* entries on this page */
+  const char* const* paths;         /* [n_entries] JSON array of inventory path segments, as gk_audit_out.paths */
+  const uint64_t* viol;             /* [n_entries][mask_words] violated constraints */
+  const uint64_t* err;              /* [n_entries][mask_words] constraints whose Matcher.Match failed (autoreject) */
+  const char* const* results_json;  /* [n_entries] with GK_VIOLATIONS_RENDER: byte for byte what gk_resident_review returns; else NULL */
+  uint64_t beyond_limits;           /* as gk_sweep_out */
+  uint64_t next_cursor;             /* 0: this was the last page */
+} gk_violations_out;
+int gk_resident_violations(gk_engine* e, uint64_t cursor, uint32_t max_objects, uint32_t flags, gk_violations_out** out);
+void gk_violations_free(gk_violations_out* o);
 /* results of one swept object, in gk_query's JSON; GK_ERR_NOT_FOUND when the object is unknown or its answer is stale */
 int gk_resident_review(gk_engine* e, const char* const* path, size_t npath, char** results_json);
 /* the same for a caller that matched itself (gk_query_ex2's arguments).  With GK_QUERY_PRE_MATCHED the sweep's bitmaps -- match AND
