@@ -8,6 +8,7 @@
 
 #include "flatten.hpp"
 #include "lower.hpp"
+#include "verify_merge.hpp"
 
 namespace gk {
 
@@ -26,6 +27,8 @@ struct EvalOptions {
                                 //   enqueue-only sweep nobody asked the duration of records no event -- the collecting call then reports 0
   bool jit_wait = true;         // wait for the plan-specialised build of the dominant kernel; false (admission batches): never
                                 //   block -- the bytecode kernel serves until the background build has been loaded
+  bool bytecode = false;        // the ahead-of-time bytecode kernel whatever the plan says: never asks for the plan-specialised build and neither
+                                //   reads nor leaves any cached launch state (the reference side of dev_verify_diff)
 };
 
 struct EvalOut {
@@ -44,6 +47,7 @@ struct EvalOut {
   uint32_t lds_bytes = 0;         // accumulator LDS per workgroup of the dominant kernel's most recent launch
   uint64_t list_bytes = 0;        // chunk lists the dominant kernel reads per launch (chunks.hpp)
   uint64_t kernel_hash = 0;       // FNV-64 of the plan-specialised kernel's source text (0: the bytecode kernel ran)
+  bool specialised = false;       // the plan-specialised code evaluated the most recent launch (the CPU stand-in: the generated plan source)
   const void *d_viol = nullptr, *d_err = nullptr, *d_counts = nullptr;   // device-resident results (valid until the table's next launch)
 };
 
@@ -64,7 +68,9 @@ DevTable* dev_table_view(DevTable* base);
 uint64_t dev_table_bytes(const DevTable* t);
 DevPlan* dev_plan_upload(int device, const HostPlan& fast, const HostPlan& big);
 void dev_plan_free(DevPlan* p);
-void dev_plan_no_jit(DevPlan* p);   // this plan is served by the bytecode kernel only (the small one-sweep-per-audit plans of the RESULT totals)
+// this plan is served by the bytecode kernel only from now on (the small one-sweep-per-audit plans of the RESULT totals; a plan group that
+// gk_table_verify quarantined).  Tables drop whatever launch state they cached for the plan: call it while no evaluation of the plan runs.
+void dev_plan_no_jit(DevPlan* p);
 void dev_eval(const DevPlan* p, const DevTable* t, const EvalOptions& opt, EvalOut* out);   // launch + finish; throws std::runtime_error
 // first-k violating reviews per bitmap row in `order` (reviews sorted by object key; grp = dense key rank, ties equal);
 // uses the bitmaps of the table's most recent evaluation.  idx: [nc][cap], n: [nc], ovf: [nc]
@@ -89,6 +95,25 @@ void dev_viol_entries(const DevTable* t, uint32_t nc, uint32_t n_reviews, const 
                       std::vector<uint32_t>* reviews, std::vector<uint64_t>* masks);
 // the violation bitmap [nc][n_tiles] of the table's most recent evaluation (device -> host copy)
 void dev_last_viol(const DevTable* t, uint32_t nc, std::vector<uint64_t>* viol);
+// ---- the plan-specialised kernel checked against the bytecode kernel (gk_table_verify).
+// dev_verify_eval: one side of a verification -- dev_eval_launch + dev_eval_finish without download; what it leaves beside the table (view)
+// is what dev_verify_diff and dev_verify_flip work on (the device: the table's result buffers themselves).  out->specialised says whether
+// the plan-specialised code ran.  dev_verify_twin: the plan the bytecode side evaluates -- nullptr where EvalOptions::bytecode selects the
+// bytecode kernel of the plan itself (the device); a backend that binds its code to the plan at upload (the CPU stand-in) uploads a twin
+// without the specialised code, which the caller keeps and frees with dev_plan_free.  dev_verify_forget: the table (view) is going away.
+void dev_verify_eval(const DevPlan* p, const DevTable* t, const EvalOptions& opt, EvalOut* out);
+DevPlan* dev_verify_twin(int device, const HostPlan& fast, const HostPlan& big);
+void dev_verify_forget(const DevTable* t);
+// dev_verify_diff: `a` holds the finished evaluation of one plan group on the specialised path, `b` -- a view of the same table -- the
+// finished evaluation of the same plan with EvalOptions::bytecode; both by dev_verify_eval, same nc and want_match.  Compared are the bits of the reviews below n_reviews that NEITHER side left
+// beyond the device's limits (too_big; their bits are unspecified) and, with `mask` (one bit per review, [ceil(n_reviews / 64)] words),
+// that are set in it.  The two too_big words are compared as a kind of their own (row 0).
+// (VerifyEntry / VerifyDiff: verify_merge.hpp)
+void dev_verify_diff(const DevTable* a, const DevTable* b, uint32_t nc, uint32_t n_reviews, bool want_match, const std::vector<uint64_t>* mask,
+                     uint32_t cap, VerifyDiff* out);
+// test aid (gk_debug_set "verify_flip"): toggle bit `review` -- with whole_word all 64 bits of its word -- of row `row` of the `kind`
+// bitmap of the table's (view's) most recent evaluation
+void dev_verify_flip(const DevTable* t, uint32_t nc, uint32_t kind, uint32_t row, uint32_t review, bool whole_word);
 // ---- multi-GPU exchange step of a sharded sweep: one communicator per engine (= per GPU / rank)
 struct DevComm;
 bool dev_comm_unique_id(char id[128], std::string* err);                                  // rank 0: ncclGetUniqueId

@@ -14,6 +14,7 @@
 #include <functional>
 #include <thread>
 #include <map>
+#include <set>
 #include <unordered_map>
 #include <unordered_set>
 #include <memory>
@@ -29,10 +30,12 @@
 #include "lower.hpp"
 #include "pe.hpp"
 #include "regex.hpp"
+#include "verify_merge.hpp"
 #include "viol_stream.hpp"
 
 using namespace gk;
 
+static std::atomic<int64_t> g_debug_verify_flip{-1};   // gk_debug_set("verify_flip", v): fault injection for gk_table_verify (gkgpu.h)
 static std::atomic<int> g_debug_group_max{0};   // gk_debug_set("group_max", n): plan groups of at most n constraints (0 = as many as fit)
 namespace {
 
@@ -303,6 +306,10 @@ struct gk_engine {
   std::vector<std::unique_ptr<Group>> extra;
   struct Variant { HostPlan fast; DevPlan* dev = nullptr; };
   std::map<std::pair<size_t, std::vector<uint16_t>>, std::unique_ptr<Variant>> variants;   // key: (plan group, capacities)
+  // plan groups (0 = the primary plan) that gk_table_verify took off the plan-specialised kernel (GK_VERIFY_QUARANTINE): every DevPlan of
+  // such a group -- the base plan, its table-sized variants, their re-uploads when the dictionary grows -- is served by the bytecode kernel
+  // until the policy set is compiled again.  Written under plan_rw exclusively.
+  std::set<size_t> quarantined;
   // plans of the "more than one result" formulas (ConstraintRec::multi_prep), evaluated by gk_table_totals only; built on its
   // first call after a policy change (totals_gen = the plan generation they belong to; guarded by totals_mu, plan_rw shared)
   std::vector<std::unique_ptr<Group>> totals_groups;
@@ -396,6 +403,9 @@ struct gk_table {
   std::vector<uint32_t> path_max;           // per element path: largest array of one review
   std::vector<DevTable*> views;             // one per extra plan group (shares the device arrays of `dev`)
   std::vector<DevTable*> tviews;            // one per totals plan group (gk_table_totals)
+  std::vector<DevTable*> vviews;            // one per plan group: the bytecode side of gk_table_verify (created by its first call)
+  std::vector<DevPlan*> vtwins;             // ... and the plans it evaluates where the backend wants plans of its own for it (dev_verify_twin;
+  uint64_t vtwins_gen = 0;                  //     nullptr on the device), of plan generation vtwins_gen
   bool resident = false;
   bool any_prematched = false;              // some review carries RF_PREMATCHED (host.rflags says which)
   uint64_t cached_gen = 0;                  // plan generation the cached variant choices belong to
@@ -515,6 +525,7 @@ DevPlan* plan_for_group(gk_engine* e, gk_table* t, size_t group, const HostPlan*
       v->fast = pb.build(pc);
       if (v->fast.scopes.size() != base.scopes.size()) throw std::runtime_error("scope layout changed");
       v->dev = dev_plan_upload(e->opts.device, v->fast, group == 0 ? e->big : e->extra[group - 1]->big);
+      if (e->quarantined.count(group)) dev_plan_no_jit(v->dev);
     } catch (const std::exception&) { v->dev = nullptr; }   // e.g. LDS limit: the default plan serves the table
     it = e->variants.emplace(key, std::move(v)).first;
   }
@@ -556,6 +567,7 @@ void ensure_plan(gk_engine* e) {
   if (e->plan_dirty || !e->dev_plan) {
     for (auto& g : e->extra) dev_plan_free(g->dev);
     e->extra.clear();
+    e->quarantined.clear();   // (new plans, new generated text: specialised afresh, to be verified afresh)
     std::vector<const ConstraintRec*> alive;
     for (auto& c : e->constraints) if (c.alive) alive.push_back(&c);
     for (auto* c : alive) if (!c->broken.empty()) throw Unsupported(c->broken);   // (a referential constraint the current inventory does not compile for)
@@ -625,6 +637,7 @@ void ensure_plan(gk_engine* e) {
   }
   if (e->dev_plan) { dev_plan_free(e->dev_plan); e->dev_plan = nullptr; }
   e->dev_plan = dev_plan_upload(e->opts.device, e->fast, e->big);
+  for (size_t g : e->quarantined) if (DevPlan* p = g == 0 ? e->dev_plan : g - 1 < e->extra.size() ? e->extra[g - 1]->dev : nullptr) dev_plan_no_jit(p);
   e->plan_gen++;
   e->plan_dirty = false;
   publish_read_set(e);
@@ -1624,6 +1637,10 @@ void gk_table_free(gk_table* t) {
   if (!t) return;
   for (DevTable* v : t->views) dev_table_free(v);
   for (DevTable* v : t->tviews) dev_table_free(v);
+  for (DevTable* v : t->views) dev_verify_forget(v);
+  for (DevTable* v : t->vviews) { dev_verify_forget(v); dev_table_free(v); }
+  for (DevPlan* p : t->vtwins) dev_plan_free(p);
+  dev_verify_forget(t->dev);
   dev_table_free(t->dev);
   delete t;
 }
@@ -2878,6 +2895,180 @@ int gk_resident_audit(gk_engine* e, uint32_t k, uint32_t flags, gk_audit_out** o
 
 void gk_audit_free(gk_audit_out* o) { if (o) delete reinterpret_cast<AuditHolder*>(o); }
 
+// ---- the plan-specialised kernel checked against the bytecode kernel (gk_table_verify, gk_resident_verify)
+namespace {
+struct VerifyHolder {
+  gk_verify_out pub;   // first member
+  std::vector<uint32_t> ids;
+  VerifyMerge m;
+  std::vector<gk_verify_entry> entries;
+  std::vector<std::string> path_text;
+  std::vector<char*> paths;
+  // over all tables verified by the call
+  uint32_t n_reviews = 0, n_plan_groups = 0, specialised_groups = 0, quarantined_groups = 0;
+  uint64_t hash = 0;
+  float a_ms = 0, b_ms = 0;
+};
+}  // namespace
+
+// One table: every plan group on the specialised path (into the table's own buffers, as gk_table_eval), again with the bytecode kernel
+// into the verification views, the comparison per group on the device, the groups merged into h->m.  `mask`: the reviews to compare
+// (nullptr: all); review_base: what the table's reviews are shifted by in the merged answer (chunks of the resident set).  The first
+// table of a call fixes the constraint ids of the rows; a later one that sees other ids fails (the policies changed in between).
+static int verify_table(gk_engine* e, gk_table* t, uint32_t flags, uint32_t max_entries, const std::vector<uint64_t>* mask, uint32_t review_base, bool first, VerifyHolder* h) {
+  ensure_plan(e);
+  if (t->dict_gen != e->dict_reg.gen())
+    return fail(GK_ERR_INVALID, "the table was flattened before a constraint with dictionary predicates was added (its <leaf>.$d rows are missing): create it again");
+  if (t->pruned && t->reads_gen != e->dict_reg.reads_gen())
+    return fail(GK_ERR_INVALID, "the pruned table was flattened before a constraint that reads other key paths was added (GK_TABLE_PRUNED): create it again");
+  if (!t->shard.shard_reviews.empty())
+    return fail(GK_ERR_INVALID, "gk_table_verify: the table is set up as a shard (gk_table_sweep_sharded), its bitmaps live in the exchange buffer: verify a table of its own");
+  const bool want_match = (flags & GK_VERIFY_WANT_MATCH) != 0;
+  std::vector<size_t> differing;   // plan groups
+  uint64_t gen = 0;
+  {
+    { std::lock_guard<std::mutex> gate(e->plan_gate); }   // (a plan change that is waiting goes first)
+    std::shared_lock<std::shared_mutex> l(e->plan_rw);
+    gen = e->plan_gen;
+    std::vector<uint32_t> ids = e->plan_ids;
+    for (auto& g : e->extra) ids.insert(ids.end(), g->ids.begin(), g->ids.end());
+    if (first) { h->ids = ids; h->m.begin((uint32_t)ids.size(), want_match); }
+    else if (ids != h->ids) return fail(GK_ERR_DEVICE, "the policies changed while the verification ran: call it again");
+    const size_t ng = 1 + e->extra.size();
+    std::vector<DevPlan*> dp(ng, nullptr);
+    std::vector<const HostPlan*> hp(ng, nullptr);
+    { std::lock_guard<std::mutex> vl(e->variants_mu); for (size_t g = 0; g < ng; g++) dp[g] = plan_for_group(e, t, g, &hp[g]); }
+    while (t->views.size() < e->extra.size()) t->views.push_back(dev_table_view(t->dev));
+    while (t->vviews.size() < ng) t->vviews.push_back(dev_table_view(t->dev));
+    // the plans of the bytecode side: the plans themselves under EvalOptions::bytecode, or the backend's twins of them (kept per plan generation)
+    if (t->vtwins_gen != gen) { for (DevPlan* p : t->vtwins) dev_plan_free(p); t->vtwins.clear(); t->vtwins_gen = gen; }
+    while (t->vtwins.size() < ng) { const size_t g = t->vtwins.size(); t->vtwins.push_back(dev_verify_twin(e->opts.device, *hp[g], g == 0 ? e->big : e->extra[g - 1]->big)); }
+    auto plan_b = [&](size_t g) { return t->vtwins[g] ? t->vtwins[g] : dp[g]; };
+    auto side_a = [&](size_t g) { return g == 0 ? t->dev : t->views[g - 1]; };
+    EvalOptions oa;
+    oa.download = false;
+    oa.want_match = want_match;
+    oa.jit_wait = true;   // whatever the table's size: the bytecode kernel is not compared with itself
+    EvalOptions ob = oa;
+    ob.bytecode = true;
+    if (ng > 1) for (size_t g = 0; g < ng; g++) dev_jit_prefetch(dp[g], side_a(g));   // (the builds compile side by side)
+    std::vector<EvalOut> A(ng), B(ng);
+    for (size_t g = 0; g < ng; g++) dev_verify_eval(dp[g], side_a(g), oa, &A[g]);
+    for (size_t g = 0; g < ng; g++) dev_verify_eval(plan_b(g), t->vviews[g], ob, &B[g]);
+    t->last_nc = (uint32_t)ids.size(); t->last_ids = ids;   // (the table's bitmaps are this evaluation's now, as after gk_table_eval)
+    // fault injection (gk_debug_set "verify_flip"): one bit or word of the bytecode side
+    const int64_t flip = g_debug_verify_flip.load();
+    const uint32_t f_kind = (uint32_t)((uint64_t)flip >> 56) & 0x7Fu, f_row = (uint32_t)((uint64_t)flip >> 32) & 0x7FFFFFu, f_review = (uint32_t)((uint64_t)flip & 0xFFFFFFFFu);
+    const bool f_word = (((uint64_t)flip >> 55) & 1u) != 0, f_here = flip >= 0 && f_review >= review_base && f_review - review_base < t->n_reviews;
+    uint32_t row_base = 0;
+    for (size_t g = 0; g < ng; g++) {
+      const uint32_t nc = A[g].n_constraints;
+      h->n_plan_groups++;
+      h->a_ms += A[g].kernel_ms; h->b_ms += B[g].kernel_ms;
+      h->hash = h->n_plan_groups == 1 ? A[g].kernel_hash : h->hash * 1099511628211ull ^ A[g].kernel_hash;   // (as gk_eval_out: one figure that names all the texts)
+      if (f_here && nc && t->n_reviews && (f_kind == VERIFY_TOO_BIG ? g == 0 : f_row >= row_base && f_row - row_base < nc))
+        dev_verify_flip(t->vviews[g], nc, f_kind, f_kind == VERIFY_TOO_BIG ? 0 : f_row - row_base, f_review - review_base, f_word);
+      // (else: no specialised build for this group -- GK_NO_JIT, a failed build, a quarantined group, whatever a backend that cannot take
+      //  a plan off its specialised code goes on running for it: nothing to compare)
+      if (A[g].specialised && !e->quarantined.count(g)) {
+        h->specialised_groups++;
+        VerifyDiff d;
+        dev_verify_diff(side_a(g), t->vviews[g], nc, t->n_reviews, want_match, mask, max_entries, &d);
+        h->m.add(d, row_base, review_base);
+        if (d.entries_total != 0 && (flags & GK_VERIFY_QUARANTINE)) differing.push_back(g);
+      }
+      row_base += nc;
+    }
+    h->n_reviews += t->n_reviews;
+  }
+  if (!differing.empty()) {
+    // nobody evaluates while a plan changes hands: the tables' cached launch state is keyed by what dev_plan_no_jit replaces
+    std::lock_guard<std::mutex> gate(e->plan_gate);
+    std::unique_lock<std::shared_mutex> l(e->plan_rw);
+    if (e->plan_gen == gen)   // (else the plans were replaced in between: verify again)
+      for (size_t g : differing) {
+        // the plan that ran -- the table-sized variant of a resident table -- and every other plan of the group: same formulas, same generator
+        e->quarantined.insert(g);
+        dev_plan_no_jit(g == 0 ? e->dev_plan : e->extra[g - 1]->dev);
+        for (auto& v : e->variants) if (v.first.first == g && v.second->dev) dev_plan_no_jit(v.second->dev);
+        h->quarantined_groups++;
+        fprintf(stderr, "[gkgpu] the plan-specialised kernel disagrees with the bytecode kernel (gk_table_verify), using the bytecode kernel for this plan\n");
+      }
+  }
+  return GK_OK;
+}
+
+static void verify_publish(VerifyHolder* h, uint32_t flags, uint32_t max_entries) {
+  h->m.finish(max_entries);
+  for (const VerifyEntry& en : h->m.entries) h->entries.push_back(gk_verify_entry{en.kind, en.row, en.review, en.a_bit});
+  gk_verify_out& p = h->pub;
+  memset(&p, 0, sizeof p);
+  p.n_reviews = h->n_reviews; p.n_constraints = (uint32_t)h->ids.size(); p.n_plan_groups = h->n_plan_groups;
+  p.constraint_ids = h->ids.data();
+  p.specialised_groups = h->specialised_groups;
+  p.kernel_text_hash = h->hash;
+  p.diff_viol = h->m.diff[0].data(); p.diff_err = h->m.diff[1].data();
+  p.diff_match = (flags & GK_VERIFY_WANT_MATCH) ? h->m.diff[2].data() : nullptr;
+  p.diff_too_big = h->m.diff_too_big; p.diff_total = h->m.diff_total();
+  p.n_entries = (uint32_t)h->entries.size(); p.entries_total = h->m.entries_total;
+  p.entries = h->entries.empty() ? nullptr : h->entries.data();
+  p.quarantined_groups = h->quarantined_groups;
+  p.specialised_ms = h->a_ms; p.bytecode_ms = h->b_ms; p.diff_ms = h->m.ms;
+}
+
+int gk_table_verify(gk_engine* e, gk_table* t, uint32_t flags, uint32_t max_entries, gk_verify_out** out) {
+  if (!e || !t || !out) return fail(GK_ERR_INVALID, "NULL argument");
+  try {
+    std::unique_ptr<VerifyHolder> h(new VerifyHolder());
+    int rc = verify_table(e, t, flags, max_entries, nullptr, 0, true, h.get());
+    if (rc != GK_OK) return rc;
+    verify_publish(h.get(), flags, max_entries);
+    *out = &h.release()->pub;
+    return GK_OK;
+  } catch (const Unsupported& ex) { return fail(GK_ERR_UNSUPPORTED, ex.what());
+  } catch (const std::exception& ex) { return fail(GK_ERR_DEVICE, ex.what()); }
+}
+
+void gk_verify_free(gk_verify_out* o) { if (o) delete reinterpret_cast<VerifyHolder*>(o); }
+
+int gk_resident_verify(gk_engine* e, uint32_t flags, uint32_t max_entries, gk_verify_out** out, char*** entry_paths) {
+  if (!e || !out) return fail(GK_ERR_INVALID, "NULL argument");
+  try {
+    gk_engine::Resident& R = e->resident;
+    std::lock_guard<std::mutex> rl(R.mu);
+    std::unique_ptr<VerifyHolder> h(new VerifyHolder());
+    uint64_t flattened = 0;
+    auto t1 = std::chrono::steady_clock::now();
+    std::vector<uint32_t> ids;
+    int rc = resident_update(e, &flattened, &t1, &ids);
+    if (rc != GK_OK) return rc;
+    R.swept = true;
+    h->ids = ids;
+    h->m.begin((uint32_t)ids.size(), (flags & GK_VERIFY_WANT_MATCH) != 0);
+    std::vector<uint32_t> base;   // first merged review of every chunk
+    uint32_t at = 0;
+    for (auto& c : R.chunks) {
+      base.push_back(at);
+      rc = verify_table(e, c.table, flags, max_entries, &c.live, at, false, h.get());   // (dead slots are not compared)
+      if (rc != GK_OK) return rc;
+      at += c.table->n_reviews;
+    }
+    verify_publish(h.get(), flags, max_entries);
+    for (const gk_verify_entry& en : h->entries) {
+      size_t ci = std::upper_bound(base.begin(), base.end(), en.review) - base.begin();
+      std::string js = "[";
+      if (ci > 0 && en.review - base[ci - 1] < R.chunks[ci - 1].obj_of_slot.size())
+        for (const std::string& seg : R.objs[R.chunks[ci - 1].obj_of_slot[en.review - base[ci - 1]]].path) { if (js.size() > 1) js += ","; json_escape(seg, js); }
+      h->path_text.push_back(js + "]");
+    }
+    for (std::string& p : h->path_text) h->paths.push_back(&p[0]);
+    if (entry_paths) *entry_paths = h->paths.empty() ? nullptr : h->paths.data();
+    *out = &h.release()->pub;
+    return GK_OK;
+  } catch (const Unsupported& ex) { return fail(GK_ERR_UNSUPPORTED, ex.what());
+  } catch (const std::exception& ex) { return fail(GK_ERR_DEVICE, ex.what()); }
+}
+
 namespace {
 // the cached answer for one resident object, as gk_query's JSON; false: not resident / not swept / its slot is stale
 // audit: the answer pkg/audit would get -- an object the Config excludes from the audit process is never reviewed ("[]")
@@ -3384,6 +3575,7 @@ int gk_debug_set(const char* key, int64_t value) {
   if (!key) return fail(GK_ERR_INVALID, "NULL argument");
   if (strcmp(key, "dict_facts") == 0) { g_debug_dict_facts.store(value != 0); return GK_OK; }
   if (strcmp(key, "group_max") == 0) { g_debug_group_max.store((int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20))); return GK_OK; }
+  if (strcmp(key, "verify_flip") == 0) { g_debug_verify_flip.store(value < 0 ? -1 : value); return GK_OK; }
   if (strcmp(key, "fold_match_labels") == 0) { g_test_fold_match_labels.store(value != 0); return GK_OK; }
   return fail(GK_ERR_NOT_FOUND, std::string("gk_debug_set: unknown key ") + key);
 }

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import copy
 import ctypes as C
+import dataclasses
 import json
 import re
 
@@ -627,6 +628,40 @@ def template_source(ct):
     return names["kind"], target.get("target"), source.get("rego"), list(source.get("libs") or [])
 
 
+@dataclasses.dataclass
+class VerifyEntry:
+    """one bit the plan-specialised kernel and the bytecode kernel disagree on"""
+    kind: str                    # "viol" | "err" | "match" | "too_big"
+    constraint_kind: str         # "" for too_big (no row) and for a constraint this driver did not add
+    constraint_name: str
+    constraint_id: int           # -1 for too_big
+    review: int                  # review of the table; for the resident set the slot counted over the chunks
+    specialised_bit: int         # the bit on the specialised side
+    path: tuple = None           # resident set: the object's inventory path
+
+
+@dataclasses.dataclass
+class VerifyResult:
+    """gk_table_verify / gk_resident_verify: ok iff the specialised kernel ran, was compared and agreed everywhere"""
+    ok: bool
+    n_reviews: int
+    n_plan_groups: int
+    specialised_groups: int
+    kernel_text_hash: int
+    constraint_ids: list
+    diff_viol: dict              # constraint id -> differing reviews
+    diff_err: dict
+    diff_match: dict             # None without want_match
+    diff_too_big: int
+    diff_total: int
+    entries_total: int
+    entries: list                # [VerifyEntry], ascending by (kind, bitmap row, review)
+    quarantined_groups: int
+    specialised_ms: float
+    bytecode_ms: float
+    diff_ms: float
+
+
 class Driver:
     """drivers.Driver backed by the MI355X engine."""
 
@@ -811,6 +846,48 @@ class Driver:
             yield from page
             if not cursor:
                 return
+
+    def _verify_result(self, out, paths=None):
+        o = out.contents
+        try:
+            ids = [int(o.constraint_ids[i]) for i in range(o.n_constraints)]
+            names = {cid: key for key, cid in self._ids.items()}
+            entries = []
+            for i in range(o.n_entries):
+                en = o.entries[i]
+                kind = L.GK_VERIFY_KINDS[en.kind]
+                cid = ids[en.row] if kind != "too_big" else -1
+                ck, cn = names.get(cid, ("", ""))
+                entries.append(VerifyEntry(kind, ck, cn, cid, int(en.review), int(en.specialised_bit),
+                                           tuple(json.loads(paths[i].decode())) if paths else None))
+            return VerifyResult(
+                ok=o.diff_total == 0 and o.specialised_groups > 0, n_reviews=int(o.n_reviews), n_plan_groups=int(o.n_plan_groups),
+                specialised_groups=int(o.specialised_groups), kernel_text_hash=int(o.kernel_text_hash), constraint_ids=ids,
+                diff_viol={cid: int(o.diff_viol[i]) for i, cid in enumerate(ids)}, diff_err={cid: int(o.diff_err[i]) for i, cid in enumerate(ids)},
+                diff_match=({cid: int(o.diff_match[i]) for i, cid in enumerate(ids)} if o.diff_match else None),
+                diff_too_big=int(o.diff_too_big), diff_total=int(o.diff_total), entries_total=int(o.entries_total), entries=entries,
+                quarantined_groups=int(o.quarantined_groups), specialised_ms=o.specialised_ms, bytecode_ms=o.bytecode_ms, diff_ms=o.diff_ms)
+        finally:
+            self.engine.lib.gk_verify_free(out)
+
+    @staticmethod
+    def _verify_flags(want_match, quarantine):
+        return (L.GK_VERIFY_WANT_MATCH if want_match else 0) | (L.GK_VERIFY_QUARANTINE if quarantine else 0)
+
+    def VerifyTable(self, table, want_match=False, quarantine=False, max_entries=64):
+        """gk_table_verify: every plan group of `table` (a Table of this driver's engine) evaluated by the plan-specialised kernel and by the
+        bytecode kernel, the bitmaps compared on the device.  quarantine: a plan group with a difference is served by the bytecode kernel
+        from now on.  -> VerifyResult"""
+        out = C.POINTER(L.gk_verify_out)()
+        self.engine._check(self.engine.lib.gk_table_verify(self.engine.handle, table.handle, self._verify_flags(want_match, quarantine), int(max_entries), C.byref(out)))
+        return self._verify_result(out)
+
+    def VerifyResident(self, want_match=False, quarantine=False, max_entries=64):
+        """gk_resident_verify: the same over the resident set (everything AddData'd), brought up to date first; dead slots are not compared and
+        every entry carries its object's inventory path.  -> VerifyResult"""
+        out, paths = C.POINTER(L.gk_verify_out)(), C.POINTER(C.c_char_p)()
+        self.engine._check(self.engine.lib.gk_resident_verify(self.engine.handle, self._verify_flags(want_match, quarantine), int(max_entries), C.byref(out), C.byref(paths)))
+        return self._verify_result(out, paths)
 
     def ResidentReviewPreMatched(self, path, constraints):
         """gk_resident_review_ex(GK_QUERY_PRE_MATCHED): the violation sets of `constraints` (the caller matched them) for one resident
@@ -1254,6 +1331,16 @@ class Client:
         if isinstance(res, ReviewFailure):
             raise res
         return res
+
+    def VerifyAudit(self, objs, namespaces=None, want_match=False, quarantine=False, max_entries=64):
+        """The canary for an audit set: the table AuditAggregate would sweep (resident, audit process), verified -- the plan-specialised kernel
+        against the bytecode kernel on the device (Driver.VerifyTable).  -> VerifyResult"""
+        rins = [to_review_in(o, namespaces[i] if namespaces else None) for i, o in enumerate(objs)]
+        table = self.driver.engine.create_table(rins, resident=True, process="audit")
+        try:
+            return self.driver.VerifyTable(table, want_match=want_match, quarantine=quarantine, max_entries=max_entries)
+        finally:
+            table.free()
 
     def AuditAggregate(self, objs, namespaces=None, limit=20, msg_size=256):
         """pkg/audit/manager.go:885-941 (addAuditResponsesToUpdateLists) for one resident set: ONE device sweep; per

@@ -418,6 +418,60 @@ int gk_resident_review(gk_engine* e, const char* const* path, size_t npath, char
 int gk_resident_review_ex(gk_engine* e, const char* const* path, size_t npath, const uint32_t* constraint_ids, size_t n_constraints,
                           uint32_t flags, char** results_json);
 
+/* ---- the plan-specialised kernel checked against the bytecode kernel (row a8/a9) ------------------------------------------
+ * The engine carries two implementations of the hot path on the same device: the plan-specialised kernel that hiprtc compiles from
+ * generated text, and the ahead-of-time bytecode interpreter that serves while a build runs.  gk_table_verify evaluates every plan
+ * group of the table with both -- the specialised side waits for its build whatever the table's size, so an admission-sized table is
+ * never "verified" by comparing the interpreter with itself -- and compares the raw bitmaps ON the device: nothing but counts and the
+ * first differences comes back.  It is the canary to run after a ROCm, driver or policy change.  It finds a DISAGREEMENT between the
+ * two kernels; what both share (flattener, lowering, the row predicates) stays the oracle's business.
+ *   - The table's own result buffers hold the specialised side's answer afterwards, exactly as gk_table_eval would have left it;
+ *     the bytecode side evaluates into views of its own that are kept with the table (one per plan group).
+ *   - The DEVICE's answers are compared: the host evaluator that completes reviews beyond the device's limits is not involved.  A
+ *     review either side left in too_big has unspecified bits and is excluded; the two too_big words are compared as a kind of their
+ *     own (GK_VERIFY_TOO_BIG, row 0; counted once per plan group that disagrees).
+ *   - specialised_groups counts the plan groups whose specialised kernel really ran and was compared.  A group whose build is
+ *     unavailable (GK_NO_JIT, a failed build, a quarantined plan) is skipped: 0 differences with specialised_groups <
+ *     n_plan_groups is NOT a pass for that group, and with specialised_groups == 0 nothing was compared at all.
+ *   - Launches enqueued with GK_EVAL_ASYNC and not yet collected are collected by the verification's own evaluation, as a
+ *     gk_table_eval without GK_EVAL_ASYNC would collect them; their timing is lost.  A table set up as a shard
+ *     (gk_table_sweep_sharded) is refused with GK_ERR_INVALID: its bitmaps live in the exchange buffer.  A stale table is refused
+ *     as by gk_table_eval.
+ *   - GK_VERIFY_QUARANTINE: every plan group with a difference is served by the bytecode kernel from now on (one line on stderr
+ *     says so), for every table: the plan that ran (the table-sized variant, for a resident table), the group's other variants and
+ *     their re-uploads when a table brings key paths the dictionary has not seen.  The quarantine lasts as long as those plans: a
+ *     policy change (template or constraint added or removed) compiles new plans, which are specialised and can be verified again.
+ * entries: at most max_entries differences, ascending by (kind, row, review); when entries_total > n_entries they are the smallest of
+ * those the device stored (max_entries per plan group), which need not be the smallest of all. */
+#define GK_VERIFY_WANT_MATCH 1u   /* compare the match bitmaps too */
+#define GK_VERIFY_QUARANTINE 2u   /* a plan group with any difference is served by the bytecode kernel from now on */
+#define GK_VERIFY_VIOL 0u         /* entry kinds */
+#define GK_VERIFY_ERR 1u
+#define GK_VERIFY_MATCH 2u
+#define GK_VERIFY_TOO_BIG 3u      /* row = 0 */
+typedef struct { uint32_t kind, row, review, specialised_bit; } gk_verify_entry;
+typedef struct {
+  uint32_t n_reviews, n_constraints, n_plan_groups;
+  const uint32_t* constraint_ids;       /* [n_constraints], bitmap-row order, as gk_eval_out */
+  uint32_t specialised_groups;          /* plan groups whose plan-specialised kernel ran and was compared; 0: nothing to compare */
+  uint64_t kernel_text_hash;            /* as gk_eval_out: names the text that was checked */
+  const uint64_t *diff_viol, *diff_err, *diff_match;   /* [n_constraints] differing reviews per row (diff_match NULL without the flag) */
+  uint64_t diff_too_big, diff_total;
+  uint32_t n_entries; uint64_t entries_total;
+  const gk_verify_entry* entries;       /* ascending by (kind, row, review); a subset of the differences when entries_total > n_entries */
+  uint32_t quarantined_groups;
+  float specialised_ms, bytecode_ms, diff_ms;   /* device time of the two evaluations and of the comparison, summed over the plan groups */
+} gk_verify_out;
+int gk_table_verify(gk_engine* e, gk_table* t, uint32_t flags, uint32_t max_entries, gk_verify_out** out);
+void gk_verify_free(gk_verify_out* o);
+/* The same over the resident set: the set is brought up to date as by gk_resident_sweep, every chunk's table is verified, the
+ * per-constraint counts are added up.  Masked-out (dead) slots are not compared.  n_reviews = the slots of all chunks; an entry's
+ * `review` is its slot counted over the chunks in order, and (*entry_paths)[i] -- when entry_paths is not NULL -- names the object of
+ * entries[i] as a JSON array of its inventory path segments (gk_audit_out.paths' form).  The array belongs to *out and goes with
+ * gk_verify_free.  specialised_groups / n_plan_groups / quarantined_groups are summed over the chunks (a resident chunk evaluates
+ * table-sized plan variants of its own). */
+int gk_resident_verify(gk_engine* e, uint32_t flags, uint32_t max_entries, gk_verify_out** out, char*** entry_paths);
+
 /* ---- admission path: micro-batched Driver.Query (row f1) ----------------------------------------------------------
  * Driver.Query evaluates ONE review (pkg/drivers/k8scel/driver.go:162-251) and the validating webhook calls it from up
  * to GOMAXPROCS request goroutines at once (pkg/webhook/policy.go:142-146, 748-757).  gk_query may be called from any
@@ -490,7 +544,10 @@ void gk_jit_cache_drop_memory(void);
  * tests/test_pruned.py reaches the totals plans a pruned table cannot answer); "group_max" (n > 0: no plan group of more than n
  * constraints, takes effect at the next policy change -- the several-group path, which a set of more than 256 distinct violation
  * formulas takes by itself, tested with small corpora; 0 = as many as fit); "dict_facts" (0: the tests on a review's non-iterated leaves
- * keep a row per leaf instead of sharing the review facts row, for the policies loaded while it is 0).  GK_ERR_NOT_FOUND for an unknown key. */
+ * keep a row per leaf instead of sharing the review facts row, for the policies loaded while it is 0); "verify_flip" (fault injection for
+ * gk_table_verify / gk_resident_verify: -1 = off, else kind << 56 | whole_word << 55 | row << 32 | review with row in the merged
+ * constraint_ids order and, for the resident set, review counted over the chunks -- the verifications that follow toggle that bit, with
+ * whole_word all 64 bits of the word that holds it, on the bytecode side before they compare).  GK_ERR_NOT_FOUND for an unknown key. */
 int gk_debug_set(const char* key, int64_t value);
 
 /* Debug: the compiled plan as text (Driver.Dump, pkg/drivers/k8scel/driver.go:253). */
