@@ -38,7 +38,7 @@ GK_VIOLATIONS_RENDER = 1
 EXPORTS = [
     "gk_engine_create", "gk_engine_destroy", "gk_last_error", "gk_version", "gk_template_add", "gk_template_remove",
     "gk_constraint_add", "gk_constraint_remove", "gk_data_put", "gk_data_remove", "gk_excluder_replace", "gk_excluder_excluded", "gk_table_create", "gk_table_free",
-    "gk_table_eval", "gk_eval_free", "gk_render", "gk_render_error", "gk_free", "gk_dump", "gk_table_topk", "gk_topk_free",
+    "gk_table_eval", "gk_eval_free", "gk_render", "gk_render_error", "gk_free", "gk_dump", "gk_table_review_words", "gk_table_topk", "gk_topk_free",
     "gk_table_totals", "gk_totals_free", "gk_table_get_stats", "gk_batcher_start", "gk_batcher_stop", "gk_query", "gk_query_ex", "gk_query_ex2",
     "gk_resident_sweep", "gk_sweep_free", "gk_resident_review", "gk_resident_review_ex", "gk_resident_audit", "gk_audit_free",
     "gk_resident_violations", "gk_violations_free", "gk_table_verify", "gk_verify_free", "gk_resident_verify",
@@ -240,6 +240,7 @@ def load(hostemu: bool | None = None):
     lib.gk_free.argtypes = [vp]
     lib.gk_free.restype = None
     lib.gk_dump.argtypes = [vp, C.POINTER(vp)]
+    lib.gk_table_review_words.argtypes = [vp, vp, C.POINTER(vp)]
     lib.gk_table_topk.argtypes = [vp, vp, u32, C.POINTER(C.POINTER(gk_topk_out))]
     lib.gk_topk_free.argtypes = [C.POINTER(gk_topk_out)]
     lib.gk_topk_free.restype = None

@@ -46,6 +46,8 @@ struct EvalOut {
   uint32_t n_launches = 0;        // launches averaged in fast_kernel_ms
   uint32_t lds_bytes = 0;         // accumulator LDS per workgroup of the dominant kernel's most recent launch
   uint64_t list_bytes = 0;        // chunk lists the dominant kernel reads per launch (chunks.hpp)
+  uint64_t rw_bytes = 0;          // review words the most recent launch read instead of rw_rows rows (rw_hdr_rows of them with their string headers) of
+  uint64_t rw_rows = 0, rw_hdr_rows = 0;   //   the plan's all-global predicate classes (review_words.hpp); 0: the sweep walked every class
   uint64_t kernel_hash = 0;       // FNV-64 of the plan-specialised kernel's source text (0: the bytecode kernel ran)
   bool specialised = false;       // the plan-specialised code evaluated the most recent launch (the CPU stand-in: the generated plan source)
   const void *d_viol = nullptr, *d_err = nullptr, *d_counts = nullptr;   // device-resident results (valid until the table's next launch)

@@ -30,12 +30,14 @@
 #include "lower.hpp"
 #include "pe.hpp"
 #include "regex.hpp"
+#include "review_words.hpp"
 #include "verify_merge.hpp"
 #include "viol_stream.hpp"
 
 using namespace gk;
 
 static std::atomic<int64_t> g_debug_verify_flip{-1};   // gk_debug_set("verify_flip", v): fault injection for gk_table_verify (gkgpu.h)
+static std::atomic<bool> g_debug_keep_slot_index{false};   // gk_debug_set("keep_slot_index", 1): tables created from now on keep the host copy of their slot index (gk_table_review_words)
 static std::atomic<int> g_debug_group_max{0};   // gk_debug_set("group_max", n): plan groups of at most n constraints (0 = as many as fit)
 namespace {
 
@@ -1518,7 +1520,7 @@ static int table_create_impl(gk_engine* e, const gk_review_in* reviews, size_t n
     t->stats.upload_s = std::chrono::duration<double>(t_up - t_indexed).count();
     t->stats.flatten_s = std::chrono::duration<double>(t_indexed - t_begin).count();
     for (size_t i = 0; i < n; i++) t->stats.json_bytes += reviews[i].json_len;
-    t->host.tile_idx.clear(); t->host.tile_idx.shrink_to_fit();
+    if (!g_debug_keep_slot_index.load()) { t->host.tile_idx.clear(); t->host.tile_idx.shrink_to_fit(); }
     *out = t.release();
     return GK_OK;
   } catch (const std::exception& ex) { return fail(GK_ERR_DEVICE, ex.what()); }
@@ -1714,6 +1716,7 @@ int gk_table_eval(gk_engine* e, gk_table* t, uint32_t flags, gk_eval_out** out) 
         o.n_overflow += og.n_overflow;
         o.kernel_ms += og.kernel_ms; o.fast_kernel_ms += og.fast_kernel_ms;
         o.list_bytes += og.list_bytes;
+        o.rw_bytes += og.rw_bytes; o.rw_rows += og.rw_rows; o.rw_hdr_rows += og.rw_hdr_rows;
         o.kernel_hash = o.kernel_hash * 1099511628211ull ^ og.kernel_hash;   // (several plan groups: one figure that names all their texts)
         o.n_constraints += og.n_constraints;
         o.d_viol = o.d_err = o.d_counts = nullptr;   // not one contiguous device buffer any more
@@ -1770,9 +1773,16 @@ int gk_table_eval(gk_engine* e, gk_table* t, uint32_t flags, gk_eval_out** out) 
       account(e->fast);
       for (auto& g : e->extra) account(g->fast);
     }
+    // (review words, review_words.hpp: a sweep whose binding evaluated the all-global classes once streams their words -- 4 B per word
+    //  and review, padded to 64 reviews -- instead of their rows; the one-off binding pass is not a per-sweep figure)
+    const uint64_t rw_rows = std::min<uint64_t>(h->out.rw_rows, rows_read), rw_hdrs = std::min<uint64_t>(h->out.rw_hdr_rows, hdrs_read);
+    rows_read -= rw_rows; hdrs_read -= rw_hdrs;
+    // (the once-per-table figures: with one plan group a hoisted slot is not streamed at all; with several, a slot hoisted by one group
+    //  may be kept by another, which the sums cannot tell -- the figure then stays the upper bound)
+    if (e->extra.empty()) { rows_once -= std::min(rows_once, rw_rows); hdrs_once -= std::min(hdrs_once, rw_hdrs); }
     p.n_rows_read = rows_read;
     (void)bound;
-    p.algo_bytes = rows_read * sizeof(Row) + hdrs_read * sizeof(StrHdr) + h->out.list_bytes +
+    p.algo_bytes = rows_read * sizeof(Row) + hdrs_read * sizeof(StrHdr) + h->out.list_bytes + h->out.rw_bytes +
                    t->dir_bytes * (1 + e->extra.size()) + plan_bytes + (uint64_t)p.n_constraints * p.n_tiles * 16 + (uint64_t)p.list_total * 8;
     p.algo_bytes_once = p.algo_bytes - (rows_read - rows_once) * sizeof(Row) - (hdrs_read - hdrs_once) * sizeof(StrHdr) - t->dir_bytes * e->extra.size();
     p.n_plan_groups = 1 + (uint32_t)e->extra.size();
@@ -3577,6 +3587,7 @@ int gk_debug_set(const char* key, int64_t value) {
   if (strcmp(key, "group_max") == 0) { g_debug_group_max.store((int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20))); return GK_OK; }
   if (strcmp(key, "verify_flip") == 0) { g_debug_verify_flip.store(value < 0 ? -1 : value); return GK_OK; }
   if (strcmp(key, "fold_match_labels") == 0) { g_test_fold_match_labels.store(value != 0); return GK_OK; }
+  if (strcmp(key, "keep_slot_index") == 0) { g_debug_keep_slot_index.store(value != 0); return GK_OK; }
   return fail(GK_ERR_NOT_FOUND, std::string("gk_debug_set: unknown key ") + key);
 }
 
@@ -3588,6 +3599,61 @@ void gk_jit_cache_stats(uint64_t* cache_hits, uint64_t* compiles) {
   dev_jit_cache_stats(&h, &c);
   if (cache_hits) *cache_hits = h;
   if (compiles) *compiles = c;
+}
+
+// Debug: what binding the primary plan to this table with review words does (review_words.hpp), computed on the host from the plan and
+// the table's slot index exactly as kernels.hip bind_chunks / bind_review_words compute it: one "key=value" per line.
+int gk_table_review_words(gk_engine* e, const gk_table* t, char** text_out) {
+  if (!e || !t || !text_out) return fail(GK_ERR_INVALID, "NULL argument");
+  try {
+    ensure_plan(e);
+    std::shared_lock<std::shared_mutex> l(e->plan_rw);
+    const HostPlan& p = e->fast;
+    const HostTable& h = t->host;
+    const uint32_t n_groups = h.n_tiles(), S = h.n_slots();
+    if (h.tile_idx.size() != (size_t)n_groups * (S + 1u)) return fail(GK_ERR_INVALID, "the table did not keep its slot index: gk_debug_set(\"keep_slot_index\", 1) before it is created");
+    std::vector<std::vector<Pred>> classes;
+    const std::vector<uint32_t> cls = jit_path_classes(p, &classes);
+    const ReviewWords rw = analyse_review_words(classes, p.dims.n_gwords);
+    std::vector<BoundPath> bound, kept, hoisted;
+    for (uint32_t s = 0; s < S; s++) {
+      const uint32_t path = h.slot_path[s];
+      if (path >= cls.size() || !cls[path]) continue;
+      const uint32_t ent = p.ptab[path];
+      bound.push_back(BoundPath{s, cls[path], pred_list_cost<Pred>(&p.path_preds[ent >> 8], ent & 0xFF, [](const Pred& q) { return pred_needs_str(q); })});
+    }
+    split_bound(bound, rw, &kept, &hoisted);
+    const int block = gk_block_of((int)h.rpt);
+    const uint32_t list_cap = (uint32_t)std::min(block / GK_TILE, 8) * GK_WAVE_CHUNKS, n_waves = (uint32_t)(block / GK_TILE);
+    const ChunkLists full = build_chunk_lists(h.tile_idx.data(), n_groups, S, bound, list_cap, n_waves);
+    const ChunkLists part = build_chunk_lists(h.tile_idx.data(), n_groups, S, kept, list_cap, n_waves);
+    // groups that hold rows of hoisted paths only: their filtered list must be a valid list of zero chunks
+    uint32_t only = 0, only_ok = 0;
+    for (uint32_t g = 0; g < n_groups; g++) {
+      const uint32_t* ix = h.tile_idx.data() + (size_t)g * (S + 1u);
+      bool any_h = false, any_k = false;
+      for (const BoundPath& b : hoisted) any_h = any_h || ix[b.slot + 1u] > ix[b.slot];
+      for (const BoundPath& b : kept) any_k = any_k || ix[b.slot + 1u] > ix[b.slot];
+      if (!any_h || any_k) continue;
+      only++;
+      const ChunkDesc& hd = part.d[(size_t)g * part.capg];
+      if (hd.st == 0u && hd.info == 0u) only_ok++;
+    }
+    uint32_t n_hoisted_classes = 0;
+    for (size_t c = 1; c < rw.hoisted.size(); c++) n_hoisted_classes += rw.hoisted[c] ? 1u : 0u;
+    std::ostringstream os;
+    os << "n_gwords=" << p.dims.n_gwords << "\nclasses=" << (classes.size() ? classes.size() - 1 : 0) << "\nhoisted_classes=" << n_hoisted_classes << "\nk=" << rw.k() << "\nwords=";
+    for (uint32_t k = 0; k < rw.k(); k++) os << (k ? "," : "") << rw.words[k];
+    os << "\nrpt=" << h.rpt << "\ngroups=" << n_groups << "\nbound_paths=" << bound.size() << "\nkept_paths=" << kept.size() << "\nhoisted_paths=" << hoisted.size()
+       << "\nchunks_full=" << full.n_chunks << "\nchunks_kept=" << part.n_chunks << "\ncapg_full=" << full.capg << "\ncapg_kept=" << part.capg
+       << "\noverflow_groups_full=" << full.n_overflow_groups << "\noverflow_groups_kept=" << part.n_overflow_groups
+       << "\ngroups_only_hoisted=" << only << "\ngroups_only_hoisted_with_empty_list=" << only_ok << "\n";
+    const std::string s = os.str();
+    char* buf = (char*)malloc(s.size() + 1);
+    memcpy(buf, s.c_str(), s.size() + 1);
+    *text_out = buf;
+    return GK_OK;
+  } catch (const std::exception& ex) { return fail(GK_ERR_INTERNAL, ex.what()); }
 }
 
 int gk_dump(gk_engine* e, char** text_out) {

@@ -13,6 +13,10 @@
 #include "codegen.hpp"
 #include "lower.hpp"
 #include "plan.hpp"
+#include "review_words.hpp"
+// kKernelBodyRw: the kernel body with the review-words hooks, made from kernel_body.inc at build time (embed_sources.py, the Makefile's
+// jit_body_rw.inc).  The two libraries include it in front of this header and define GK_HAVE_BODY_RW; a program that compiles this header
+// alone gets the plain text only and an exception where it asks for the variant.
 
 namespace gk {
 
@@ -114,8 +118,21 @@ inline std::string jit_res_macros() {
 }
 
 // plan_hpp / vm_core_hpp / kernel_body: plan.hpp, vm_core.hpp and kernel_body.inc as text (build/jit_sources.inc)
+// rw_words: the global words of the plan's review-word classes (review_words.hpp) -- set and not empty: the text is the REVIEW-WORDS
+// variant (two more kernel parameters; the words of a review come from the binding's array instead of the hoisted classes' chunks);
+// unset: today's text.  GK_JIT_REVIEW_WORDS=force (tuning / test aid): the variant for every plan that has such classes, whoever asks --
+// the GPU-less build dumps it that way and puts it through hiprtc (tests/test_review_words_text.py).
 inline std::string assemble_jit_source(const HostPlan& plan, uint32_t rpt, uint32_t rpp, const char* plan_hpp,
-                                       const char* vm_core_hpp, const char* kernel_body, uint32_t list_cap = 0) {
+                                       const char* vm_core_hpp, const char* kernel_body, uint32_t list_cap = 0,
+                                       const std::vector<uint32_t>* rw_words = nullptr) {
+  std::vector<uint32_t> rw_forced;
+  if (const char* f = getenv("GK_JIT_REVIEW_WORDS"); !rw_words && f && std::string(f) == "force") {
+    std::vector<std::vector<Pred>> classes;
+    jit_path_classes(plan, &classes);
+    rw_forced = analyse_review_words(classes, plan.dims.n_gwords).words;
+    rw_words = &rw_forced;
+  }
+  const bool rw = rw_words && !rw_words->empty();
   std::string src =
       "typedef unsigned char uint8_t; typedef unsigned short uint16_t; typedef unsigned int uint32_t; typedef unsigned long long uint64_t;\n"
       "typedef short int16_t; typedef int int32_t; typedef long long int64_t;\n";
@@ -170,6 +187,11 @@ inline std::string assemble_jit_source(const HostPlan& plan, uint32_t rpt, uint3
   src += "#define GK_RPT_K " + std::to_string(rpt) + "\n#define GK_RPP_K " + std::to_string(rpp) + "\n";
   if (list_cap) src += "#define GK_LIST_CAP_K " + std::to_string(list_cap) + "\n";
   if (const uint32_t tk = jit_tot_k(plan.dims.n_constraints, (size_t)plan.dims.acc_words * rpp * 4, rpt, block, jit_res_k(plan), list_cap ? list_cap : list_cap_of(block))) src += "#define GK_TOT_K " + std::to_string(tk) + "\n";   // (kernel_body.inc: per-constraint totals left as one row per workgroup)
+  if (rw) {   // (kernel_body.inc as embed_sources.py extends it: GK_RW_K words per review, word GK_RW_WORD(k) of the accumulators each)
+    std::string sel = "0u";
+    for (size_t k = rw_words->size(); k-- > 0;) sel = "(k) == " + std::to_string(k) + "u ? " + std::to_string((*rw_words)[k]) + "u : " + sel;
+    src += "#define GK_RW_K " + std::to_string(rw_words->size()) + "\n#define GK_RW_WORD(k) (" + sel + ")\n";
+  }
   if (const char* defs = getenv("GK_JIT_DEFINES")) {   // tuning aid: "A=1;B" -> #define A 1, #define B (kernel_body.inc variants)
     std::string d = defs, item;
     for (size_t i = 0; i <= d.size(); i++) {
@@ -189,6 +211,12 @@ inline std::string assemble_jit_source(const HostPlan& plan, uint32_t rpt, uint3
     while (fgets(buf, sizeof buf, f)) { line = buf; if (line.rfind("#include", 0) != 0 && line.rfind("#pragma once", 0) != 0) body += line; }
     fclose(f);
     src += body;
+  } else if (rw) {
+#ifdef GK_HAVE_BODY_RW
+    src += kKernelBodyRw;
+#else
+    throw std::runtime_error("the review-words kernel body is not part of this build");
+#endif
   } else src += kernel_body;
   src += "}\n";
   return src;

@@ -564,6 +564,19 @@ class Engine:
         self._check(self.lib.gk_table_create(self.handle, reviews_ptr, n, flags, st, C.byref(h)))
         return Table(self, h, st, n)
 
+    def table_review_words(self, table):
+        """gk_table_review_words: what binding the primary plan to `table` with review words leaves out of the sweep's lists, as a dict
+        (`words`: list of ints, everything else int).  The table must have been created under gk_debug_set("keep_slot_index", 1)."""
+        p = C.c_void_p()
+        self._check(self.lib.gk_table_review_words(self.handle, table.handle, C.byref(p)))
+        s = C.string_at(p).decode()
+        self.lib.gk_free(p)
+        out = {}
+        for line in s.splitlines():
+            k, _, v = line.partition("=")
+            out[k] = [int(x) for x in v.split(",") if x] if k == "words" else int(v)
+        return out
+
     def dump(self):
         p = C.c_void_p()
         self._check(self.lib.gk_dump(self.handle, C.byref(p)))

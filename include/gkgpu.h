@@ -552,6 +552,12 @@ int gk_debug_set(const char* key, int64_t value);
 
 /* Debug: the compiled plan as text (Driver.Dump, pkg/drivers/k8scel/driver.go:253). */
 int gk_dump(gk_engine* e, char** text_out);
+/* Debug: what binding the primary plan to `t` with review words leaves out of the sweep's chunk lists (the predicate classes evaluated
+ * once per plan and table), as "key=value" lines: n_gwords, classes, hoisted_classes, k, words, rpt, groups, bound_paths, kept_paths,
+ * hoisted_paths, chunks_full, chunks_kept, capg_full, capg_kept, overflow_groups_full, overflow_groups_kept, groups_only_hoisted,
+ * groups_only_hoisted_with_empty_list.  Needs the table's slot index on the host: gk_debug_set("keep_slot_index", 1) before the table
+ * is created (GK_ERR_INVALID otherwise).  Free the text with gk_free. */
+int gk_table_review_words(gk_engine* e, const gk_table* t, char** text_out);
 
 #ifdef __cplusplus
 }
