@@ -15,6 +15,7 @@
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -88,6 +89,42 @@ inline DX dx_node(DExpr::Kind k, std::vector<DX> args, const std::string& name =
 
 inline const std::string& dx_to_string(const DX& e) { return e->text; }
 
+// VALUE EXPRESSIONS: a leaf-local expression whose VALUE is compared with another review value travels in a synthetic scalar row
+// <leaf>.$v<id> beside its leaf (flatten.hpp DictRegistry::add_vexpr; the flattener evaluates it per distinct leaf value).  <id> is a
+// hash of the canonical text: the same derivation names the same row in every constraint, whatever was loaded before it -- formulas
+// are normalised and shared by their path text.  The expression is kept under its name (the lowering registers it from there); a name
+// that two different texts hash to is refused.
+struct DxValueNames { std::mutex mu; std::map<std::string, DX> by_name; };
+inline DxValueNames& dx_value_names() { static DxValueNames r; return r; }
+inline bool dx_is_value_key(const std::string& key) { return key.size() > 2 && key[0] == '$' && key[1] == 'v'; }
+inline std::string dx_value_name(const DX& dx) {
+  uint64_t h = 1469598103934665603ull;
+  for (unsigned char ch : dx->text) { h ^= ch; h *= 1099511628211ull; }
+  static const char* hex = "0123456789abcdef";
+  std::string name = "$v";
+  for (int i = 15; i >= 4; i--) name.push_back(hex[(h >> (4 * i)) & 15]);   // 48 bits
+  DxValueNames& r = dx_value_names();
+  std::lock_guard<std::mutex> l(r.mu);
+  auto it = r.by_name.find(name);
+  if (it == r.by_name.end()) r.by_name.emplace(name, dx);
+  else if (it->second->text != dx->text) throw std::runtime_error("two value expressions share the row name " + name);
+  return name;
+}
+inline DX dx_value_expr(const std::string& name) {   // nullptr: no expression was ever named so
+  DxValueNames& r = dx_value_names();
+  std::lock_guard<std::mutex> l(r.mu);
+  auto it = r.by_name.find(name);
+  return it == r.by_name.end() ? nullptr : it->second;
+}
+// can the expression be evaluated on a SCALAR leaf alone?  Not when it looks inside a container (a deep call, a rebuilt sub-document)
+// or sizes the leaf itself (count of the leaf: arrays and objects have one)
+inline bool dx_scalar_leaf(const DX& e) {
+  if (e->kind == DExpr::CALL && (dx_is_user(e->name) || e->name == "$wrap")) return false;
+  if (e->kind == DExpr::CALL && e->name == "count" && e->args.size() == 1 && e->args[0]->kind == DExpr::LEAF) return false;
+  for (auto& a : e->args) if (!dx_scalar_leaf(a)) return false;
+  return true;
+}
+
 inline bool dx_cmp_holds(int c, int op) {
   switch (op) { case 0: return c == 0; case 1: return c != 0; case 2: return c < 0; case 3: return c <= 0; case 4: return c > 0; default: return c >= 0; }
 }
@@ -98,6 +135,15 @@ inline Value dx_eval(const DX& e, const Value& leaf) {
     case DExpr::LEAF: return leaf;
     case DExpr::CONST: return e->c;
     case DExpr::CALL: {
+      if (e->name == "$pick") {   // $pick(cond1, value1, cond2, value2 ..): the value of the first body whose condition holds and whose value is defined
+        for (size_t i = 0; i + 1 < e->args.size(); i += 2) {
+          const Value c = dx_eval(e->args[i], leaf);
+          if (!(c.is_bool() && c.b)) continue;
+          Value v = dx_eval(e->args[i + 1], leaf);
+          if (v.defined()) return v;
+        }
+        return Value();
+      }
       ValueVec av;
       for (auto& a : e->args) { Value v = dx_eval(a, leaf); if (!v.defined()) return Value(); av.push_back(v); }
       if (dx_is_user(e->name)) return dx_call_user(e->name, av);
@@ -107,6 +153,7 @@ inline Value dx_eval(const DX& e, const Value& leaf) {
         for (size_t i = av[1].size(); i-- > 0;) { ValuePairs p; p.emplace_back(av[1].items()[i], v); v = Value::object(std::move(p)); }
         return v;
       }
+      if (e->name == "$list") return Value::array(std::move(av));   // an array literal of leaf-local values (the operands of a sprintf)
       if (e->name == "$index") {   // element of an array (a split component); negative index: from the end; out of range: undefined
         if (av.size() != 2 || !av[0].is_array() || !av[1].is_number() || !av[1].is_int) return Value();
         const long long n = (long long)av[0].size();

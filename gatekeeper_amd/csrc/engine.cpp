@@ -758,6 +758,37 @@ std::shared_ptr<const PreparedConstraint> prepare_multi(gk_engine* e, const Temp
   }
 }
 
+// A constraint left while value expressions are registered (flatten.hpp DictRegistry::add_vexpr): the registry is emptied and the
+// constraints that stay register what they need again, by the steps that registered it when they were added and in that order -- the
+// counting forms' keys and dictionary expressions, then the trial lowering of the violation formula.  What only the constraint that
+// left had asked for is gone: no value rows, no dictionary bits, no carrier rows, no ranks on its account -- tables and plans are what
+// they were before it came.  (Without value expressions the registry stays append-only, as it always was.)  Caller holds mu exclusively.
+void reregister_values(gk_engine* e) {
+  if (!e->dict_reg.has_vexprs()) return;
+  e->dict_reg.reset_all();
+  for (auto& c : e->constraints) {
+    if (!c.alive) continue;
+    try {
+      auto it = e->templates.find(lower_str(c.kind));
+      c.count_ready = false; c.count_rows.clear(); c.count_flag = nullptr;
+      if (it != e->templates.end() && !c.referential) {
+        PrepMemoScope memo;
+        const Template::CountInfo ci = it->second->compile_all(c.params, &e->next_quant);
+        c.cforms = derive_count_forms(e, ci, c.mf, nullptr, &c.count_reads);
+      } else {
+        c.cforms = nullptr;   // (a referential constraint: its results are counted by rendering until the inventory compiles it again)
+        c.count_reads.clear();
+      }
+      if (c.prep) {
+        PlanBuilder pb(&e->dict, &e->dict_reg);
+        pb.add_constraint(c.prep);
+        PlanCaps caps;
+        pb.build(caps);
+      }
+    } catch (const std::exception&) {}   // (it compiled and lowered when it was added; ensure_plan words whatever is wrong with it now)
+  }
+}
+
 // ---- referential templates (data.inventory) ----------------------------------------------------------------------------------
 // data.inventory as one document, from the mirror of the synced objects (caller holds mu exclusively)
 const Value& current_inventory(gk_engine* e) {
@@ -993,6 +1024,7 @@ int gk_template_remove(gk_engine* e, const char* kind) {
   std::string k = lower_str(kind);
   if (!e->templates.erase(k)) return fail(GK_ERR_NOT_FOUND, "unknown template " + k);
   for (auto& c : e->constraints) if (lower_str(c.kind) == k) c.alive = false;
+  reregister_values(e);
   e->plan_dirty = true;
   return GK_OK;
 }
@@ -1082,6 +1114,7 @@ int gk_constraint_remove(gk_engine* e, const char* kind, const char* name) {
   bool found = false;
   for (auto& c : e->constraints) if (c.alive && c.kind == kind && c.name == name) { c.alive = false; found = true; }
   if (!found) return fail(GK_ERR_NOT_FOUND, std::string("unknown constraint ") + kind + "/" + name);
+  reregister_values(e);
   e->plan_dirty = true;
   return GK_OK;
 }
@@ -3674,6 +3707,8 @@ int gk_dump(gk_engine* e, char** text_out) {
       std::shared_lock<std::shared_mutex> rl(e->mu);
       for (auto& c : e->constraints) if (c.alive) os << "constraint " << c.id << " " << c.kind << "/" << c.name << " viol: " << f_to_string(c.viol) << "\n";
     }
+    // value expressions (flatten.hpp DictRegistry::add_vexpr): "<leaf pattern> $v<id> = <expression>[ ordered]", one line each
+    if (e->dict_reg.has_vexprs()) os << "value expressions:\n" << e->dict_reg.dump_vexprs();
     std::string s = os.str();
     char* buf = (char*)malloc(s.size() + 1);
     memcpy(buf, s.c_str(), s.size() + 1);

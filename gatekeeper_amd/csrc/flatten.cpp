@@ -317,6 +317,55 @@ bool DictRegistry::ordered(const PathDict& dict, uint32_t path_id) const {
   for (const auto& g : ordered_) if (pattern_matches(g.second, dict, path_id)) return true;
   return false;
 }
+bool DictRegistry::add_vexpr(const Pattern& row, const DX& dx, bool add) {
+  if (row.size() < 2 || row.back().any || !dx_is_value_key(row.back().key) || !dx) throw std::runtime_error("not a value row: " + pattern_to_string(row));
+  const Pattern leaf(row.begin(), row.end() - 1);
+  const std::string lk = pattern_to_string(leaf), &name = row.back().key;
+  std::unique_lock<std::shared_mutex> l(mu_);
+  for (const VExpr& v : vexprs_)
+    if (v.leaf_key == lk && v.name == name) {
+      if (v.dx->text != dx->text) throw std::runtime_error("two value expressions share the row name " + name);   // (the full text decides, never the hash)
+      return true;
+    }
+  if (!add) return false;
+  vexprs_.push_back(VExpr{leaf, name, lk, dx});
+  n_vexprs_.store((uint32_t)vexprs_.size(), std::memory_order_release);
+  gen_++;   // tables flattened before this lack the rows: they are stale (engine.cpp dict_gen)
+  return true;
+}
+void DictRegistry::match_vexprs(const PathDict& dict, uint32_t leaf_path_id, std::vector<VExpr>* out) const {
+  out->clear();
+  if (!has_vexprs()) return;
+  std::shared_lock<std::shared_mutex> l(mu_);
+  for (const VExpr& v : vexprs_) {
+    if (!pattern_matches(v.leaf, dict, leaf_path_id)) continue;
+    // (two patterns may cover one leaf -- an element loop and a flat wildcard predicate: the row is named by the expression, written once)
+    bool dup = false;
+    for (const VExpr& o : *out) if (o.name == v.name) dup = true;
+    if (!dup) out->push_back(v);
+  }
+}
+void DictRegistry::reset_all() {
+  std::unique_lock<std::shared_mutex> l(mu_);
+  pats_.clear(); guards_.clear(); values_.clear(); ordered_.clear(); keys_.clear(); carriers_.clear(); vexprs_.clear();
+  n_vexprs_.store(0, std::memory_order_release);
+  n_ordered_.store(0, std::memory_order_release);
+  gen_++;   // (never back to an earlier generation: a table flattened under any earlier state stays stale)
+  if (counting_) counting_->reset_all();
+}
+std::string DictRegistry::dump_vexprs() const {
+  std::shared_lock<std::shared_mutex> l(mu_);
+  std::vector<std::string> lines;
+  for (const VExpr& v : vexprs_) {
+    bool ord = false;
+    for (const auto& g : ordered_) if (g.first.size() >= v.name.size() && g.first.compare(g.first.size() - v.name.size(), v.name.size(), v.name) == 0 && pattern_to_string(Pattern(g.second.begin(), g.second.end() - 1)) == v.leaf_key) ord = true;
+    lines.push_back(v.leaf_key + " " + v.name + " = " + v.dx->text + (ord ? " ordered" : ""));
+  }
+  std::sort(lines.begin(), lines.end());
+  std::string o;
+  for (const std::string& s : lines) { o += s; o += "\n"; }
+  return o;
+}
 bool DictRegistry::set_reads(const std::vector<Pattern>& pats) {
   std::vector<std::pair<std::string, Pattern>> v;
   for (const Pattern& p : pats) v.emplace_back(pattern_to_string(p), p);
@@ -356,6 +405,7 @@ void DictRegistry::interest(std::vector<const Pattern*>* out) const {
   for (auto& g : guards_) out->push_back(&g.second);
   for (auto& g : values_) out->push_back(&g.second);
   for (auto& g : keys_) out->push_back(&g.second);
+  for (auto& v : vexprs_) out->push_back(&v.leaf);   // (the LEAF of a value expression is parsed even where no predicate reads its own rows)
 }
 uint32_t DictRegistry::read_state(const PathDict& dict, uint32_t path_id) const {
   const uint64_t stp = stamp();
@@ -675,7 +725,11 @@ bool Flattener::dict_wanted(uint32_t path) {
     reg_->match(*dict_, path, &d.entries, &d.pat, &d.facts);
     d.centries.clear(); d.cpat = -1;
     if (const DictRegistry* c = reg_->counting_if_any()) c->match(*dict_, path, &d.centries, &d.cpat);
-    d.state = d.entries.empty() && d.centries.empty() ? 1 : 2;
+    // value expressions of the leaf (DictRegistry::add_vexpr): their rows are written where the dictionary rows are
+    d.ventries.clear(); d.vpaths.clear(); d.vmemo.reset();
+    reg_->match_vexprs(*dict_, path, &d.ventries);
+    for (const DictRegistry::VExpr& v : d.ventries) d.vpaths.push_back(child(path, v.name));
+    d.state = d.entries.empty() && d.centries.empty() && d.ventries.empty() ? 1 : 2;
     d.deep = false;
     for (const DictEntry& e : d.entries) if (dx_deep(e.dx)) d.deep = true;
     for (const DictEntry& e : d.centries) if (dx_deep(e.dx)) d.deep = true;
@@ -693,7 +747,80 @@ bool Flattener::guard_wanted(uint32_t path) {
   return d.gstate == 2;
 }
 
+// The VALUE ROWS of a leaf: <leaf>.$v<id> holds the value of a registered expression for this leaf, as a scalar row with the leaf's
+// element ordinals -- from there on a review path like any other (its rows get value ids: the row pattern is a value pattern).  The
+// evaluator is dx_eval, the one the renderer uses; answers are remembered per distinct leaf value, and a column of (nearly) unique
+// values stops filling the memo, as for the dictionary rows.  Undefined (a builtin error, no function body applies): no row -- every
+// relation on it is false.  What no id can stand for -- a non-empty container, an integer beyond int64 -- sends the review to the
+// host evaluator (RF_HOST_CAND), as a non-empty container on a compared leaf does.
+void Flattener::value_rows(uint32_t path, uint32_t meta, const Value& leaf) {
+  emit_side_effects_ = true;   // (never replayed from a Namespace's recorded rows: value ids, review flags)
+  // a row WITHOUT a value id: the kernels refuse a review in which a compared row has none, and the engine completes it on the host
+  auto no_id_row = [&](uint32_t vp, uint32_t m, uint32_t lo, uint32_t hi) {
+    review_flags_ |= RF_HOST_CAND;
+    if (emit(vp, m, lo, hi)) stage_.back().row.rev &= ROW_REV_MASK;
+  };
+  const uint32_t base = meta & ~(uint32_t)ROW_TYPE_MASK & ~(uint32_t)ROW_STR_INLINE & ~(uint32_t)ROW_INEXACT;
+  if ((leaf.is_array() || leaf.is_object() || leaf.is_set()) && leaf.size() != 0) {
+    // (a non-empty container leaf arrives as a placeholder of its size: nothing can be evaluated on it)
+    for (size_t i = 0; i < dict_paths_[path].vpaths.size(); i++) no_id_row(dict_paths_[path].vpaths[i], base | T_ARRAY, (uint32_t)leaf.size(), 0);
+    return;
+  }
+  std::vector<Value> vals;
+  {
+    DictPath& d = dict_paths_[path];
+    if (!d.vmemo) d.vmemo.reset(new ValMemo());
+    ValMemo& M = *d.vmemo;
+    bool use = true, hit = false;
+    std::string key;
+    if (M.bypass_left) { M.bypass_left--; use = false; }
+    else {
+      key = leaf.is_string() ? leaf.str() : to_term_string(leaf);
+      key.push_back((char)('0' + (int)leaf.kind));
+      auto it = M.map.find(key);
+      if (it != M.map.end()) { vals = it->second; hit = true; }
+      M.hits += hit ? 1u : 0u;
+      if (++M.seen == 8192u) { if (M.hits * 8u < M.seen) M.bypass_left = 7u * 8192u; M.seen = M.hits = 0; }
+    }
+    if (!hit) {
+      for (const DictRegistry::VExpr& e : d.ventries) vals.push_back(dx_eval(e.dx, leaf));
+      if (use && M.map.size() < 65536) M.map.emplace(std::move(key), vals);
+    }
+  }
+  for (size_t i = 0; i < vals.size(); i++) {
+    const uint32_t vp = dict_paths_[path].vpaths[i];   // (emit() may grow dict_paths_: looked up per row)
+    const Value& v = vals[i];
+    if (!v.defined()) continue;
+    if (v.is_null()) emit(vp, base | T_NULL, 0, 0);
+    else if (v.is_bool()) emit(vp, base | T_BOOL, v.b ? 1 : 0, 0);
+    else if (v.is_string()) emit_string_row(vp, base, v.str());
+    else if (v.is_number()) {
+      if (v.is_int) {
+        if (v.i < (i128)INT64_MIN || v.i > (i128)INT64_MAX) {   // (no double holds it exactly: never ranked, never guessed)
+          const double dv = v.as_double();
+          uint64_t u;
+          memcpy(&u, &dv, 8);
+          no_id_row(vp, base | T_FLOAT | ROW_INEXACT, (uint32_t)u, (uint32_t)(u >> 32));
+          continue;
+        }
+        const uint64_t u = (uint64_t)(int64_t)v.i;
+        emit(vp, base | T_INT, (uint32_t)u, (uint32_t)(u >> 32));
+      } else {
+        const double dv = v.as_double();
+        uint64_t u;
+        memcpy(&u, &dv, 8);
+        emit(vp, base | T_FLOAT, (uint32_t)u, (uint32_t)(u >> 32));
+      }
+    } else if (v.size() == 0 && (v.is_array() || v.is_object())) emit(vp, base | (v.is_array() ? T_ARRAY : T_OBJECT), 0, 0);
+    else no_id_row(vp, base | (v.is_object() ? T_OBJECT : T_ARRAY), (uint32_t)v.size(), 0);   // a derived non-empty container (split ..): its equality would need a deep comparison
+  }
+}
+
 void Flattener::dict_row(uint32_t path, uint32_t meta, const Value& leaf, uint64_t* masks_out) {
+  if (!dict_paths_[path].ventries.empty() && !masks_out) {
+    value_rows(path, meta, leaf);
+    if (dict_paths_[path].entries.empty() && dict_paths_[path].centries.empty()) return;
+  }
   DictPath& d = dict_paths_[path];
   // containers count by type and size only (the registered expressions cannot look inside them: pe.cpp scalar_fns) -- unless
   // an expression of this path is DEEP (dexpr.hpp): then the leaf is the real sub-document and the memo goes by its text
@@ -729,6 +856,10 @@ void Flattener::dict_row(uint32_t path, uint32_t meta, const Value& leaf, uint64
 // dict_row for a STRING leaf given as bytes: the answers are remembered per path under the bytes themselves (no Value, no quoted
 // term text, no std::string key per row -- the dictionary leaves of a policy set are mostly strings: images, quantities, names)
 void Flattener::dict_row_str(uint32_t path, uint32_t meta, const char* s, uint32_t n, uint64_t* masks_out, bool use_memo) {
+  if (!dict_paths_[path].ventries.empty() && !masks_out) {
+    value_rows(path, meta, Value::string(std::string(s, n)));
+    if (dict_paths_[path].entries.empty() && dict_paths_[path].centries.empty()) return;
+  }
   if (!use_memo) {   // a leaf whose values are as good as unique (a match candidate's name): straight evaluation where the expressions allow
     DictPath& d = dict_paths_[path];
     bool ok = true;
@@ -1081,11 +1212,15 @@ void Flattener::walk(const Value& v, uint32_t path, uint32_t ords, int adepth, u
   switch (v.kind) {
     case Value::Null: emit(path, meta | T_NULL, 0, 0); if (dict_wanted(path)) dict_row(path, meta, v); break;
     case Value::Bool: emit(path, meta | T_BOOL, v.b ? 1 : 0, 0); if (dict_wanted(path)) dict_row(path, meta, v); break;
-    case Value::Number:
-      if (dict_wanted(path)) dict_row(path, meta, v);
+    case Value::Number: {
+      // (the one-pass parsers emit an integer of up to 18 digits before its dictionary row, every other number after it: the same order
+      //  here -- a value row interns a value id, and ids in order of first occurrence must not depend on the ingest path)
+      const bool short_int = v.is_int && v.i > -(i128)1000000000000000000ll && v.i < (i128)1000000000000000000ll;
+      if (!short_int && dict_wanted(path)) dict_row(path, meta, v);
       if (v.is_int && v.i >= (i128)INT64_MIN && v.i <= (i128)INT64_MAX) {
         uint64_t u = (uint64_t)(int64_t)v.i;
         emit(path, meta | T_INT, (uint32_t)u, (uint32_t)(u >> 32));
+        if (short_int && dict_wanted(path)) dict_row(path, meta, v);
       } else {
         double d = v.as_double();
         uint64_t u;
@@ -1093,6 +1228,7 @@ void Flattener::walk(const Value& v, uint32_t path, uint32_t ords, int adepth, u
         emit(path, meta | T_FLOAT | (v.is_int ? ROW_INEXACT : 0), (uint32_t)u, (uint32_t)(u >> 32));
       }
       break;
+    }
     case Value::String: emit_string_row(path, meta, v.str()); if (dict_wanted(path)) dict_row(path, meta, v); break;
     case Value::Object: {
       emit(path, meta | T_OBJECT, (uint32_t)v.size(), 0);

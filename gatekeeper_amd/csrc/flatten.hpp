@@ -121,6 +121,20 @@ class DictRegistry {
   bool valued(const PathDict& dict, uint32_t path_id) const;
   bool has_ordered() const { return n_ordered_.load(std::memory_order_acquire) != 0; }
   bool ordered(const PathDict& dict, uint32_t path_id) const;   // (not cached here: the flattener asks once per path, and only for inexact numbers)
+  // Value expressions: leaf-local expressions whose VALUE the loaded constraints compare with other review values.  `row` = the
+  // pattern of the synthetic row <leaf>.$v<id> (dexpr.hpp dx_value_name); the flattener evaluates `dx` on every scalar leaf matching
+  // the pattern without its last step and writes the result there, a scalar row with the leaf's ordinals (no row: undefined).  The row
+  // pattern is a value pattern like any other (add_value gives its rows ids).  A new expression makes earlier tables stale (gen).
+  struct VExpr { Pattern leaf; std::string name /* "$v<id>" */, leaf_key /* pattern_to_string(leaf) */; DX dx; };
+  bool add_vexpr(const Pattern& row, const DX& dx, bool add = true);   // false: not registered (and add = false); throws std::runtime_error when the name holds another expression
+  void match_vexprs(const PathDict& dict, uint32_t leaf_path_id, std::vector<VExpr>* out) const;
+  bool has_vexprs() const { return n_vexprs_.load(std::memory_order_acquire) != 0; }
+  // forgets EVERYTHING the constraints registered -- dictionary expressions (both spaces), guards, value and key patterns, carriers,
+  // value expressions -- and moves gen: the caller registers again what the constraints that are still loaded need, in the order they
+  // were added (engine.cpp reregister_values), so that a registry which held a removed constraint's entries is the registry it
+  // would be without it.  (The read set stays: ensure_plan publishes it with the next plan.)
+  void reset_all();
+  std::string dump_vexprs() const;   // one line per expression: "<leaf pattern> $v<id> = <dx text>[ ordered]"
   // Message keys (round 4, result counting: pe.hpp Template::count_forms): leaf patterns whose values lead the messages of a
   // per-element violation.  A review in which two rows of such paths hold the SAME value -- or one that is no scalar -- gets the
   // synthetic row  review.$dup : true ; the counting plans then leave the review's pairs to the host renderer.
@@ -156,6 +170,8 @@ class DictRegistry {
   std::vector<std::pair<std::string, Pattern>> guards_, values_, keys_;
   std::vector<std::pair<std::string, Pattern>> ordered_;   // the value patterns an ordering relation reads (a subset of values_)
   std::atomic<uint32_t> n_ordered_{0};
+  std::vector<VExpr> vexprs_;
+  std::atomic<uint32_t> n_vexprs_{0};
   struct Carrier { std::string key; Pattern elem; std::string member; };
   std::vector<Carrier> carriers_;
   std::atomic<uint64_t> gen_{0};
@@ -361,11 +377,14 @@ class Flattener {
                    // a column of (nearly) unique values -- image tags pinned by digest, generated names -- only fills the memo: after a window of
                    // 8192 look-ups with fewer than one hit in eight the next seven windows evaluate straight (round 6)
                    uint32_t seen = 0, hits = 0, bypass_left = 0; };
-  struct DictPath { std::unique_ptr<StrMemo> smemo; int state = 0; int gstate = 0; int vstate = 0; int ostate = 0 /* an ORDERED value path: 0 unknown, 1 no, 2 yes */; int kstate = 0; uint32_t rstate = 0 /* 4 | read_state once known */; int pat = -1; std::unique_ptr<DxStrProg> sprog[2] /* the entries / centries compiled for string values (dexpr.hpp) */; bool facts = false /* the main-space answers go to the review facts row, review.$r.$d */; bool deep = false /* some expression looks inside a container leaf */; std::vector<DictEntry> entries; uint32_t dpath = 0; std::unordered_map<std::string, uint64_t> memo;   // state 0 unknown, 1 none, 2 has entries
+  struct ValMemo { std::unordered_map<std::string, std::vector<Value>> map; uint32_t seen = 0, hits = 0, bypass_left = 0; };   // distinct leaf value -> the values of the leaf's value expressions (the window rule of StrMemo)
+  struct DictPath { std::vector<DictRegistry::VExpr> ventries; std::vector<uint32_t> vpaths /* their rows: <leaf>.$v<id> */; std::unique_ptr<ValMemo> vmemo;
+                    std::unique_ptr<StrMemo> smemo; int state = 0; int gstate = 0; int vstate = 0; int ostate = 0 /* an ORDERED value path: 0 unknown, 1 no, 2 yes */; int kstate = 0; uint32_t rstate = 0 /* 4 | read_state once known */; int pat = -1; std::unique_ptr<DxStrProg> sprog[2] /* the entries / centries compiled for string values (dexpr.hpp) */; bool facts = false /* the main-space answers go to the review facts row, review.$r.$d */; bool deep = false /* some expression looks inside a container leaf */; std::vector<DictEntry> entries; uint32_t dpath = 0; std::unordered_map<std::string, uint64_t> memo;   // state 0 unknown, 1 none, 2 has entries
                     int cpat = -1; std::vector<DictEntry> centries; uint32_t cpath = 0; std::unordered_map<std::string, uint64_t> cmemo; /* the counting space: <leaf>.$c */ };
   std::vector<DictPath> dict_paths_;
   void dict_row(uint32_t path, uint32_t meta, const Value& leaf, uint64_t* masks_out = nullptr);   // emits <leaf>.$d / .$c when some registered expression is true (masks_out: hands the two masks back instead)
   void dict_row_str(uint32_t path, uint32_t meta, const char* s, uint32_t n, uint64_t* masks_out = nullptr, bool use_memo = true);
+  void value_rows(uint32_t path, uint32_t meta, const Value& leaf);   // emits <leaf>.$v<id> for every value expression registered on the leaf
   void match_fact(uint32_t path, const char* s, uint32_t n, uint64_t* acc, bool use_memo = true);   // one fact of a match candidate: string row + dictionary answers
   void match_group_row(int w, const uint64_t* acc);                            // review.$m.<o|old>.$d / .$c
   bool dict_wanted(uint32_t path);

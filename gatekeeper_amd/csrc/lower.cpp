@@ -422,41 +422,7 @@ static FP simplify_impl(const FP& f) {
 FP rename_f(const FP& f, const std::map<int, int>& m);
 
 // ---- dictionary predicates (dexpr.hpp): every boolean sub-formula that talks about ONE leaf only and contains a DICT atom
-// becomes a single DICT atom, evaluated by the flattener per distinct value of that leaf.
-bool dict_foldable_atom(const Atom& a) {
-  switch (a.kind) {
-    case Atom::DICT: case Atom::TYPE: case Atom::TRUTHY: case Atom::DEFINED: case Atom::STR_PREFIX: case Atom::STR_SUFFIX: case Atom::STR_CONTAINS:
-    case Atom::STR_IN_SET: case Atom::STR_REGEX: case Atom::COUNT_CMP: case Atom::SPLIT_CMP: case Atom::SPLIT_COUNT: case Atom::SPLIT_PREFIX: return true;
-    case Atom::CMP: return !(a.k.is_array() || a.k.is_object() || a.k.is_set());
-    default: return false;
-  }
-}
-// leaf of a leaf-local formula ("" = not leaf-local); has_dict: it contains a DICT atom
-static std::string leaf_of_uncached(const FP& f, bool* has_dict);
-std::string leaf_of(const FP& f, bool* has_dict) {
-  if (f->leaf_state == 0) {   // (asked again and again for the same sub-formulas while conjunctions are folded per leaf)
-    bool d = false;
-    f->leaf_text = leaf_of_uncached(f, &d);
-    f->leaf_state = d ? 2 : 1;
-  }
-  if (f->leaf_state == 2 && !f->leaf_text.empty()) *has_dict = true;
-  return f->leaf_text;
-}
-static std::string leaf_of_uncached(const FP& f, bool* has_dict) {
-  switch (f->kind) {
-    case FNode::ATOM:
-      if (!dict_foldable_atom(f->atom)) return "";
-      if (f->atom.kind == Atom::DICT) *has_dict = true;
-      return spath_to_string(f->atom.path);
-    case FNode::NOT: return leaf_of(f->kids[0], has_dict);
-    case FNode::AND: case FNode::OR: {
-      std::string l;
-      for (auto& k : f->kids) { std::string x = leaf_of(k, has_dict); if (x.empty() || (!l.empty() && x != l)) return ""; l = x; }
-      return l;
-    }
-    default: return "";
-  }
-}
+// becomes a single DICT atom, evaluated by the flattener per distinct value of that leaf.  (dict_foldable_atom, leaf_of, to_dx: pe.cpp)
 // is the formula false whenever its leaf is absent? (device predicates only fire on rows that exist)
 static bool needs_leaf_uncached(const FP& f);
 bool needs_leaf(const FP& f) {
@@ -475,49 +441,6 @@ const SPath* leaf_path_of(const FP& f) {
   if (f->kind == FNode::ATOM) return &f->atom.path;
   for (auto& k : f->kids) if (const SPath* p = leaf_path_of(k)) return p;
   return nullptr;
-}
-DX to_dx(const FP& f) {
-  switch (f->kind) {
-    case FNode::T: return dx_const(Value::boolean(true));
-    case FNode::F: return dx_const(Value::boolean(false));
-    case FNode::NOT: return dx_node(DExpr::NOT, {to_dx(f->kids[0])});
-    case FNode::AND: case FNode::OR: { std::vector<DX> a; for (auto& k : f->kids) a.push_back(to_dx(k)); return dx_node(f->kind == FNode::AND ? DExpr::AND : DExpr::OR, a); }
-    case FNode::ATOM: {
-      const Atom& a = f->atom;
-      switch (a.kind) {
-        case Atom::DICT: return a.dx;
-        case Atom::DEFINED: return dx_const(Value::boolean(true));   // the expression is only evaluated for leaves that exist
-        case Atom::TRUTHY: return dx_node(DExpr::TRUTHY, {dx_leaf()});
-        case Atom::TYPE: return dx_node(DExpr::TYPE_MASK, {dx_leaf()}, "", 0, a.mask);
-        case Atom::CMP: return dx_node(DExpr::CMP, {dx_leaf(), dx_const(a.k)}, "", a.cmp);
-        case Atom::STR_PREFIX: return dx_node(DExpr::TRUTHY, {dx_node(DExpr::CALL, {dx_leaf(), dx_const(a.k)}, "startswith")});
-        case Atom::STR_SUFFIX: return dx_node(DExpr::TRUTHY, {dx_node(DExpr::CALL, {dx_leaf(), dx_const(a.k)}, "endswith")});
-        case Atom::STR_CONTAINS: return dx_node(DExpr::TRUTHY, {dx_node(DExpr::CALL, {dx_leaf(), dx_const(a.k)}, "contains")});
-        case Atom::STR_REGEX: return dx_node(DExpr::TRUTHY, {dx_node(DExpr::CALL, {dx_const(a.k), dx_leaf()}, "re_match")});
-        case Atom::COUNT_CMP:   // member count of a container leaf (the flattener hands containers over with their size)
-          return dx_node(DExpr::AND, {dx_node(DExpr::TYPE_MASK, {dx_leaf()}, "", 0, (1u << T_ARRAY) | (1u << T_OBJECT)), dx_node(DExpr::CMP, {dx_node(DExpr::CALL, {dx_leaf()}, "count"), dx_const(a.k)}, "", a.cmp)});
-        case Atom::STR_IN_SET: { std::vector<DX> alts; for (auto& v : a.k.items()) alts.push_back(dx_node(DExpr::CMP, {dx_leaf(), dx_const(v)}, "", C_EQ)); return dx_node(DExpr::OR, alts); }
-        case Atom::SPLIT_CMP: case Atom::SPLIT_COUNT: case Atom::SPLIT_PREFIX: {
-          // split(trim(leaf, cut), sep) as the partial evaluator spells it (pe.cpp leaf_local); a leaf that is no string, a component
-          // that does not exist: the builtin / $index is undefined and the comparison false -- what the row predicates answer
-          DX base = dx_leaf();
-          if (a.cut) base = dx_node(DExpr::CALL, {base, dx_const(Value::string(std::string(1, a.cut)))}, "trim");
-          if (a.kind == Atom::SPLIT_PREFIX) {   // trim(s) == P  |  startswith(trim(s), P + sep)      (P = the components joined by sep)
-            std::string joined;
-            for (size_t i = 0; i < a.k.items().size(); i++) { if (i) joined.push_back(a.sep); joined += a.k.items()[i].str(); }
-            return dx_node(DExpr::OR, {dx_node(DExpr::CMP, {base, dx_const(Value::string(joined))}, "", C_EQ),
-                                       dx_node(DExpr::TRUTHY, {dx_node(DExpr::CALL, {base, dx_const(Value::string(joined + std::string(1, a.sep)))}, "startswith")})});
-          }
-          DX arr = dx_node(DExpr::CALL, {base, dx_const(Value::string(std::string(1, a.sep)))}, "split");
-          if (a.kind == Atom::SPLIT_COUNT) return dx_node(DExpr::CMP, {dx_node(DExpr::CALL, {arr}, "count"), dx_const(a.k)}, "", a.cmp);
-          return dx_node(DExpr::CMP, {dx_node(DExpr::CALL, {arr, dx_const(Value::integer(a.idx))}, "$index"), dx_const(a.k)}, "", a.cmp);
-        }
-        default: break;
-      }
-    }
-    default: break;
-  }
-  throw Unsupported("unsupported on the device plan: formula is not leaf-local");
 }
 FP dict_atom(const SPath& leaf, DX dx, FP alt = nullptr) { Atom a; a.kind = Atom::DICT; a.path = leaf; a.dx = std::move(dx); a.alt = std::move(alt); return f_atom(a); }
 
@@ -1797,6 +1720,16 @@ HostPlan PlanBuilder::build(const PlanCaps& caps) {
       g.op = P_TYPE; g.dst = D_GLOBAL; g.bit = 0; g.ctype = (uint8_t)(1u << T_OBJECT);
       L.plan.preds.push_back(g);
       L.plan.pred_patterns.push_back(prefix);
+    }
+    // a predicate on a VALUE ROW <leaf>.$v<id> (pe.cpp value_row_path): the flattener writes the row once the expression behind the
+    // name is registered on the leaf's pattern -- a frozen plan lives with the expressions the loaded constraints registered
+    for (size_t i = 0; i < L.plan.preds.size(); i++) {
+      const Pattern& pat = L.plan.pred_patterns[i];
+      if (pat.size() < 2 || pat.back().any || !dx_is_value_key(pat.back().key)) continue;
+      const DX dx = dx_value_expr(pat.back().key);
+      bool have = false;
+      try { have = dx && reg_->add_vexpr(pat, dx, !frozen_); } catch (const std::runtime_error& ex) { throw Unsupported(std::string("unsupported on the device plan: ") + ex.what()); }
+      if (!have) throw Unsupported("unsupported on the device plan: needs value ids no loaded constraint registered");
     }
     // rows that are compared with other review values need VALUE IDS: the flattener assigns them on the registered paths
     for (size_t i = 0; i < L.plan.preds.size(); i++)

@@ -270,18 +270,67 @@ bool leaf_local(const SVP& v, SPath* leaf, DX* dx) {
 SVP sv_derived(const SPath& leaf, DX dx) { SV s; s.kind = SV::DERIVED; s.path = leaf; s.dx = std::move(dx); return mksv(std::move(s)); }
 FP f_dict(const SPath& leaf, DX dx) { Atom a; a.kind = Atom::DICT; a.path = leaf; a.dx = std::move(dx); return f_atom(a); }
 // operands of one operation: constants and values derived from the SAME leaf -> their expressions
+// (the operands' merged-body expressions, SV::pdx, of the same_leaf_args call that just succeeded: derived_of builds the result's from them)
+thread_local std::vector<DX> g_arg_pdx;
+thread_local bool g_arg_pdx_any = false;
 bool same_leaf_args(const std::vector<SVP>& args, SPath* leaf, std::vector<DX>* dxs) {
   bool have = false;
   dxs->clear();
+  g_arg_pdx.clear(); g_arg_pdx_any = false;
   for (const SVP& a : args) {
-    if (a->kind == SV::CONST) { if (!a->c.defined()) return false; dxs->push_back(dx_const(a->c)); continue; }
+    if (a->kind == SV::CONST) { if (!a->c.defined()) return false; dxs->push_back(dx_const(a->c)); g_arg_pdx.push_back(dxs->back()); continue; }
     SPath p; DX d;
     if (!leaf_local(a, &p, &d)) return false;
     if (have && spath_to_string(p) != spath_to_string(*leaf)) return false;
     *leaf = p; have = true;
     dxs->push_back(d);
+    g_arg_pdx.push_back(a->pdx ? a->pdx : d);
+    g_arg_pdx_any = g_arg_pdx_any || a->pdx != nullptr;
   }
   return have;
+}
+// the value `kind`(dxs) of the leaf whose operands same_leaf_args just gave: DERIVED, with the merged-body expression carried along
+SVP derived_of(const SPath& leaf, DExpr::Kind kind, const std::vector<DX>& dxs, const std::string& name) {
+  SV s; s.kind = SV::DERIVED; s.path = leaf; s.dx = dx_node(kind, dxs, name);
+  if (g_arg_pdx_any && g_arg_pdx.size() == dxs.size()) s.pdx = dx_node(kind, g_arg_pdx, name);
+  return mksv(std::move(s));
+}
+// An operand of a comparison between two review values, as a PATH whose rows carry value ids: a review leaf is itself; a value computed
+// from ONE scalar leaf -- a builtin chain, arithmetic with constants, a split component, a sprintf of the leaf -- is the leaf's
+// synthetic row <leaf>.$v<id> (dexpr.hpp dx_value_name), which the flattener writes beside the leaf with the expression's value.
+// false: no such row can stand for the operand (a key, a container, a deep or narrowed call, values of several leaves)
+bool value_row_path(const SVP& v, SPath* out) {
+  if (v->kind == SV::PATH && !v->pdx) { if (v->path.empty()) return false; *out = v->path; return true; }
+  SPath leaf; DX dx;
+  if ((v->kind == SV::PATH || v->kind == SV::DERIVED) && v->pdx) {   // one body of a function over the leaf: the function's value, whichever body applies
+    if (v->path.empty() || (v->kind == SV::DERIVED && v->idx == 1)) return false;
+    leaf = v->path; dx = v->pdx;
+  } else if (v->kind == SV::OPAQUE) {
+    // sprintf(<constant format>, [leaf, ..]) with known parts (fmt_parts): every operand the same review leaf, no constant operand
+    // folded into the text (hsig: the format, then one entry per operand)
+    if (v->elems.empty() || v->hsig.size() < 2) return false;
+    std::vector<DX> ops;
+    for (const CondElem& e : v->elems) {
+      if (e.v->kind == SV::CONST) continue;
+      if (e.v->kind != SV::PATH || e.v->path.empty() || !e.cond || e.cond->kind != FNode::T) return false;
+      if (!ops.empty() && spath_to_string(e.v->path) != spath_to_string(leaf)) return false;
+      leaf = e.v->path;
+      ops.push_back(dx_leaf());
+    }
+    if (ops.empty() || ops.size() + 1 != v->hsig.size()) return false;
+    for (size_t i = 1; i < v->hsig.size(); i++) if (v->hsig[i].empty() || v->hsig[i][0] != 'P') return false;
+    dx = dx_node(DExpr::CALL, {dx_const(Value::string(v->hsig[0])), dx_node(DExpr::CALL, ops, "$list")}, "sprintf");
+  } else if (v->kind == SV::DERIVED || v->kind == SV::STRX) {   // (split(leaf, sep) itself: a non-empty array, which the flattener leaves to the host evaluator)
+    if (!leaf_local(v, &leaf, &dx) || leaf.empty()) return false;
+  } else return false;
+  if (!dx_scalar_leaf(dx)) return false;
+  if (dx->kind != DExpr::LEAF) {
+    Step st;
+    try { st.key = dx_value_name(dx); } catch (const std::runtime_error& ex) { throw Unsupported(std::string("unsupported on the device plan: ") + ex.what()); }
+    leaf.push_back(st);
+  }
+  *out = leaf;
+  return true;
 }
 constexpr uint32_t M_STRING = 1u << T_STRING, M_NUMBER = (1u << T_INT) | (1u << T_FLOAT), M_BOOL = 1u << T_BOOL,
                    M_NULL = 1u << T_NULL, M_ARRAY = 1u << T_ARRAY, M_OBJECT = 1u << T_OBJECT;
@@ -316,6 +365,95 @@ int cmp_of(const std::string& op) {
 }
 
 }  // namespace
+
+// ---- leaf-local formulas as expressions of their leaf (dexpr.hpp).  Here, not in lower.cpp: the partial evaluator asks too
+// (merge_leaf_bodies), and the host-only builds link this unit without the lowering.
+bool dict_foldable_atom(const Atom& a) {
+  switch (a.kind) {
+    case Atom::DICT: case Atom::TYPE: case Atom::TRUTHY: case Atom::DEFINED: case Atom::STR_PREFIX: case Atom::STR_SUFFIX: case Atom::STR_CONTAINS:
+    case Atom::STR_IN_SET: case Atom::STR_REGEX: case Atom::COUNT_CMP: case Atom::SPLIT_CMP: case Atom::SPLIT_COUNT: case Atom::SPLIT_PREFIX: return true;
+    case Atom::CMP: return !(a.k.is_array() || a.k.is_object() || a.k.is_set());
+    default: return false;
+  }
+}
+// leaf of a leaf-local formula ("" = not leaf-local); has_dict: it contains a DICT atom
+static std::string leaf_of_uncached(const FP& f, bool* has_dict);
+std::string leaf_of(const FP& f, bool* has_dict) {
+  if (f->leaf_state == 0) {   // (asked again and again for the same sub-formulas while conjunctions are folded per leaf)
+    bool d = false;
+    f->leaf_text = leaf_of_uncached(f, &d);
+    f->leaf_state = d ? 2 : 1;
+  }
+  if (f->leaf_state == 2 && !f->leaf_text.empty()) *has_dict = true;
+  return f->leaf_text;
+}
+static std::string leaf_of_uncached(const FP& f, bool* has_dict) {
+  switch (f->kind) {
+    case FNode::ATOM:
+      if (!dict_foldable_atom(f->atom)) return "";
+      if (f->atom.kind == Atom::DICT) *has_dict = true;
+      return spath_to_string(f->atom.path);
+    case FNode::NOT: return leaf_of(f->kids[0], has_dict);
+    case FNode::AND: case FNode::OR: {
+      std::string l;
+      for (auto& k : f->kids) { std::string x = leaf_of(k, has_dict); if (x.empty() || (!l.empty() && x != l)) return ""; l = x; }
+      return l;
+    }
+    default: return "";
+  }
+}
+DX to_dx(const FP& f) {
+  switch (f->kind) {
+    case FNode::T: return dx_const(Value::boolean(true));
+    case FNode::F: return dx_const(Value::boolean(false));
+    case FNode::NOT: return dx_node(DExpr::NOT, {to_dx(f->kids[0])});
+    case FNode::AND: case FNode::OR: { std::vector<DX> a; for (auto& k : f->kids) a.push_back(to_dx(k)); return dx_node(f->kind == FNode::AND ? DExpr::AND : DExpr::OR, a); }
+    case FNode::ATOM: {
+      const Atom& a = f->atom;
+      switch (a.kind) {
+        case Atom::DICT: return a.dx;
+        case Atom::DEFINED: return dx_const(Value::boolean(true));   // the expression is only evaluated for leaves that exist
+        case Atom::TRUTHY: return dx_node(DExpr::TRUTHY, {dx_leaf()});
+        case Atom::TYPE: return dx_node(DExpr::TYPE_MASK, {dx_leaf()}, "", 0, a.mask);
+        case Atom::CMP: return dx_node(DExpr::CMP, {dx_leaf(), dx_const(a.k)}, "", a.cmp);
+        case Atom::STR_PREFIX: return dx_node(DExpr::TRUTHY, {dx_node(DExpr::CALL, {dx_leaf(), dx_const(a.k)}, "startswith")});
+        case Atom::STR_SUFFIX: return dx_node(DExpr::TRUTHY, {dx_node(DExpr::CALL, {dx_leaf(), dx_const(a.k)}, "endswith")});
+        case Atom::STR_CONTAINS: return dx_node(DExpr::TRUTHY, {dx_node(DExpr::CALL, {dx_leaf(), dx_const(a.k)}, "contains")});
+        case Atom::STR_REGEX: return dx_node(DExpr::TRUTHY, {dx_node(DExpr::CALL, {dx_const(a.k), dx_leaf()}, "re_match")});
+        case Atom::COUNT_CMP:   // member count of a container leaf (the flattener hands containers over with their size)
+          return dx_node(DExpr::AND, {dx_node(DExpr::TYPE_MASK, {dx_leaf()}, "", 0, (1u << T_ARRAY) | (1u << T_OBJECT)), dx_node(DExpr::CMP, {dx_node(DExpr::CALL, {dx_leaf()}, "count"), dx_const(a.k)}, "", a.cmp)});
+        case Atom::STR_IN_SET: { std::vector<DX> alts; for (auto& v : a.k.items()) alts.push_back(dx_node(DExpr::CMP, {dx_leaf(), dx_const(v)}, "", C_EQ)); return dx_node(DExpr::OR, alts); }
+        case Atom::SPLIT_CMP: case Atom::SPLIT_COUNT: case Atom::SPLIT_PREFIX: {
+          // split(trim(leaf, cut), sep) as the partial evaluator spells it (pe.cpp leaf_local); a leaf that is no string, a component
+          // that does not exist: the builtin / $index is undefined and the comparison false -- what the row predicates answer
+          DX base = dx_leaf();
+          if (a.cut) base = dx_node(DExpr::CALL, {base, dx_const(Value::string(std::string(1, a.cut)))}, "trim");
+          if (a.kind == Atom::SPLIT_PREFIX) {   // trim(s) == P  |  startswith(trim(s), P + sep)      (P = the components joined by sep)
+            std::string joined;
+            for (size_t i = 0; i < a.k.items().size(); i++) { if (i) joined.push_back(a.sep); joined += a.k.items()[i].str(); }
+            return dx_node(DExpr::OR, {dx_node(DExpr::CMP, {base, dx_const(Value::string(joined))}, "", C_EQ),
+                                       dx_node(DExpr::TRUTHY, {dx_node(DExpr::CALL, {base, dx_const(Value::string(joined + std::string(1, a.sep)))}, "startswith")})});
+          }
+          DX arr = dx_node(DExpr::CALL, {base, dx_const(Value::string(std::string(1, a.sep)))}, "split");
+          if (a.kind == Atom::SPLIT_COUNT) return dx_node(DExpr::CMP, {dx_node(DExpr::CALL, {arr}, "count"), dx_const(a.k)}, "", a.cmp);
+          return dx_node(DExpr::CMP, {dx_node(DExpr::CALL, {arr, dx_const(Value::integer(a.idx))}, "$index"), dx_const(a.k)}, "", a.cmp);
+        }
+        default: break;
+      }
+    }
+    default: break;
+  }
+  throw Unsupported("unsupported on the device plan: formula is not leaf-local");
+}
+// a formula that talks about ONE leaf as an expression of that leaf (pe.hpp: the partial evaluator asks when it merges the bodies of a
+// function over one leaf into one value expression); false: not leaf-local, or about another leaf
+bool leaf_formula_dx(const FP& f, const std::string& leaf_text, DX* dx) {
+  if (f->kind == FNode::T) { *dx = dx_const(Value::boolean(true)); return true; }
+  bool has_dict = false;
+  if (leaf_of(f, &has_dict) != leaf_text) return false;
+  try { *dx = to_dx(f); } catch (const Unsupported&) { return false; }
+  return true;
+}
 
 class PE {
  public:
@@ -723,6 +861,21 @@ class PE {
 
   // ---------------------------------------------------------------------------------------------- predicates
  public:
+  // a relation between the values at two review paths (leaves, or the value rows of computed values: value_row_path)
+  static FP value_paths_f(const SPath& pa, int op, const SPath& pb) {
+    Atom c = atom_path(Atom::VEQ, pa);
+    c.path2 = pb;
+    if (op != C_EQ && op != C_NE) {
+      // an ORDERING relation under Rego's total order: the same atom carrying its relation, operands in the order written.  The
+      // device compares the two value ids, which are ranks once an ordered pattern is registered (lower.cpp F_VCMP); a missing
+      // side makes the relation false, as it makes the expression undefined
+      c.cmp = op;
+      return f_atom(c);
+    }
+    FP eq = f_atom(c);
+    if (op == C_EQ) return eq;
+    return f_and(f_and(f_atom(atom_path(Atom::DEFINED, pa)), f_atom(atom_path(Atom::DEFINED, pb))), f_not(eq));
+  }
   FP compare_f(const SVP& a, int op, const SVP& b) {
     if (a->kind == SV::CONST && b->kind == SV::CONST) {
       if (!a->c.defined() || !b->c.defined()) return f_false();
@@ -738,7 +891,16 @@ class PE {
     if (a->kind == SV::DERIVED || b->kind == SV::DERIVED) {   // a computation on one leaf against a constant / the same leaf
       SPath leaf; std::vector<DX> dx;
       if (same_leaf_args({a, b}, &leaf, &dx)) return f_dict(leaf, dx_node(DExpr::CMP, {dx[0], dx[1]}, "", op));
+      // values of two different leaves: each computed side is read from its leaf's value row <leaf>.$v<id>, and the comparison is
+      // the one between two review paths
+      SPath pa, pb;
+      if (value_row_path(a, &pa) && value_row_path(b, &pb)) return value_paths_f(pa, op, pb);
       unsupported("comparison between values derived from different review fields");
+    }
+    if (b->kind != SV::CONST && (a->kind == SV::STRX || a->kind == SV::OPAQUE || b->kind == SV::STRX || b->kind == SV::OPAQUE)) {
+      // (a trimmed string, a split component or a formatted leaf against another review value: the same rows)
+      SPath pa, pb;
+      if (value_row_path(a, &pa) && value_row_path(b, &pb) && spath_to_string(pa) != spath_to_string(pb)) return value_paths_f(pa, op, pb);
     }
     switch (a->kind) {
       case SV::OPAQUE:
@@ -770,20 +932,11 @@ class PE {
           c.cmp = op; c.k = k;
           return f_atom(c);
         }
-        if (b->kind == SV::PATH) {
-          Atom c = atom_path(Atom::VEQ, a->path);
-          c.path2 = b->path;
-          if (op != C_EQ && op != C_NE) {
-            // an ORDERING relation under Rego's total order: the same atom carrying its relation, operands in the order written.  The
-            // device compares the two value ids, which are ranks once an ordered pattern is registered (lower.cpp F_VCMP); a missing
-            // side makes the relation false, as it makes the expression undefined
-            c.cmp = op;
-            return f_atom(c);
-          }
-          FP eq = f_atom(c);
-          if (op == C_EQ) return eq;
-          return f_and(f_and(f_atom(atom_path(Atom::DEFINED, a->path)), f_atom(atom_path(Atom::DEFINED, b->path))), f_not(eq));
+        if (b->kind == SV::PATH && (a->pdx || b->pdx)) {   // (the body of a function that returns its argument: the function's value row, as for its other bodies)
+          SPath pa, pb;
+          if (value_row_path(a, &pa) && value_row_path(b, &pb)) return value_paths_f(pa, op, pb);
         }
+        if (b->kind == SV::PATH) return value_paths_f(a->path, op, b->path);
         break;
       case SV::KEYOF:
         if (b->kind == SV::CONST && b->c.is_number() && op != C_EQ && op != C_NE) {
@@ -1461,7 +1614,7 @@ class PE {
     }
     {   // arithmetic on one review leaf: recorded as an expression of that leaf (dexpr.hpp)
       SPath leaf; std::vector<DX> dx;
-      if (!(a->kind == SV::STRX) && !(b->kind == SV::STRX) && same_leaf_args({a, b}, &leaf, &dx)) return sv_derived(leaf, dx_node(DExpr::ARITH, {dx[0], dx[1]}, op));
+      if (!(a->kind == SV::STRX) && !(b->kind == SV::STRX) && same_leaf_args({a, b}, &leaf, &dx)) return derived_of(leaf, DExpr::ARITH, dx, op);
     }
     if (a->kind == SV::STRX && a->xkind == SV::XCOUNT && b->kind == SV::CONST && b->c.is_number() && b->c.is_int && (op == "-" || op == "+")) {
       SV c = *a;
@@ -1524,7 +1677,7 @@ class PE {
       if (user) {
         if (concrete_) { call_function(fpkg, fname, args, s2, r, out); return; }
         const size_t mark = out.size();
-        try { call_function(fpkg, fname, args, s2, r, out); return; }
+        try { call_function(fpkg, fname, args, s2, r, out); merge_leaf_bodies(args, s2, mark, out); return; }
         catch (const Unsupported&) {
           out.resize(mark);
           if (!deep_call(fpkg, fname, args, s2, out)) throw;   // (a closed helper over ONE sub-document goes to the flattener: dexpr.hpp)
@@ -1557,6 +1710,35 @@ class PE {
   }
 
   FP all_defined(const SVP& v) { return defined_f(v); }
+
+  // The bodies of a function applied to ONE scalar review leaf (canonify_cpu's three spellings of a quantity): each alternative keeps
+  // its value and its conditions, and learns the function's value as ONE expression of the leaf, SV::pdx = $pick(cond1, value1, ..) --
+  // where every body's value and every condition it adds is an expression of that leaf.  Nothing reads it but a comparison with a
+  // value of another leaf (value_row_path), where the function then takes one value row and one value slot, not one per body: the
+  // pairs of bodies share one atom, guarded by their conditions as before.
+  void merge_leaf_bodies(const std::vector<SVP>& args, const State& s, size_t mark, Vals& out) {
+    if (out.size() < mark + 2) return;
+    SPath leaf; std::vector<DX> adx;
+    if (!same_leaf_args(args, &leaf, &adx) || leaf.empty()) return;
+    for (const DX& d : adx) if (!dx_scalar_leaf(d)) return;
+    const std::string lt = spath_to_string(leaf);
+    std::vector<DX> pick;
+    for (size_t i = mark; i < out.size(); i++) {
+      const Val& v = out[i];
+      if (v.s.quants.size() != s.quants.size() || v.s.conds.size() < s.conds.size()) return;
+      for (size_t k = 0; k < s.conds.size(); k++) if (v.s.conds[k].get() != s.conds[k].get()) return;
+      if (v.v->kind != SV::PATH && v.v->kind != SV::DERIVED) return;
+      SPath p; DX vdx;
+      if (!leaf_local(v.v, &p, &vdx) || spath_to_string(p) != lt || !dx_scalar_leaf(vdx)) return;
+      if (v.v->pdx) vdx = v.v->pdx;
+      std::vector<DX> cs;
+      for (size_t k = s.conds.size(); k < v.s.conds.size(); k++) { DX c; if (!leaf_formula_dx(v.s.conds[k], lt, &c)) return; cs.push_back(c); }
+      pick.push_back(cs.empty() ? dx_const(Value::boolean(true)) : cs.size() == 1 ? cs[0] : dx_node(DExpr::AND, cs));
+      pick.push_back(vdx);
+    }
+    const DX m = dx_node(DExpr::CALL, pick, "$pick");
+    for (size_t i = mark; i < out.size(); i++) { SV c = *out[i].v; c.pdx = m; out[i].v = mksv(std::move(c)); }
+  }
 
   // ---------------------------------------------------------------------------------------------- deep calls (dexpr.hpp)
   // Is the function CLOSED: do its bodies (and everything they call or refer to in the package) read nothing but their
@@ -1769,7 +1951,7 @@ class PE {
         push_bool(f_atom(t), f_atom(d));
         return;
       }
-      { SPath leaf; std::vector<DX> dx; if (same_leaf_args(a, &leaf, &dx)) { out.push_back({sv_derived(leaf, dx_node(DExpr::CALL, dx, name)), s}); return; } }
+      { SPath leaf; std::vector<DX> dx; if (same_leaf_args(a, &leaf, &dx)) { out.push_back({derived_of(leaf, DExpr::CALL, dx, name), s}); return; } }
       unsupported(name + " with these symbolic operands", line);
     }
     if (name == "re_match" || name == "regex.match") {
@@ -1783,7 +1965,7 @@ class PE {
         push_bool(f_atom(at), f_type(a[1]->path, M_STRING));
         return;
       }
-      { SPath leaf; std::vector<DX> dx; if (same_leaf_args(a, &leaf, &dx)) { out.push_back({sv_derived(leaf, dx_node(DExpr::CALL, dx, name)), s}); return; } }
+      { SPath leaf; std::vector<DX> dx; if (same_leaf_args(a, &leaf, &dx)) { out.push_back({derived_of(leaf, DExpr::CALL, dx, name), s}); return; } }
       unsupported(name + " with these symbolic operands", line);
     }
     if (name == "strings.any_prefix_match" || name == "strings.any_suffix_match") {
@@ -1837,7 +2019,7 @@ class PE {
         out.push_back({mksv(std::move(x)), s});
         return;
       }
-      { SPath leaf; std::vector<DX> dx; if (same_leaf_args(a, &leaf, &dx)) { out.push_back({sv_derived(leaf, dx_node(DExpr::CALL, dx, name)), s}); return; } }
+      { SPath leaf; std::vector<DX> dx; if (same_leaf_args(a, &leaf, &dx)) { out.push_back({derived_of(leaf, DExpr::CALL, dx, name), s}); return; } }
       unsupported("trim() with these operands on review data", line);
     }
     if (name == "split") {
@@ -1906,7 +2088,7 @@ class PE {
           "trim_prefix", "trim_suffix", "startswith", "endswith", "contains", "re_match", "regex.match", "indexof", "abs", "round", "ceil", "floor", "format_int",
           "concat" /* of a constant separator and the split() of the leaf */};
       SPath leaf; std::vector<DX> dx;
-      if (scalar_fns.count(name) && same_leaf_args(a, &leaf, &dx)) { out.push_back({sv_derived(leaf, dx_node(DExpr::CALL, dx, name)), s}); return; }
+      if (scalar_fns.count(name) && same_leaf_args(a, &leaf, &dx)) { out.push_back({derived_of(leaf, DExpr::CALL, dx, name), s}); return; }
     }
     unsupported("builtin " + name + " applied to review data", line);
   }

@@ -68,7 +68,7 @@ struct FNode {
   // once made (mkf / f_* reset the cache of a copy they are handed); formulas are built and lowered under the engine's locks
   mutable std::string canon;
   mutable bool canon_set = false;
-  // (lower.cpp leaf_of, cached the same way: the leaf of a leaf-local formula, "" = not leaf-local; whether it holds a DICT atom)
+  // (leaf_of, cached the same way: the leaf of a leaf-local formula, "" = not leaf-local; whether it holds a DICT atom)
   mutable std::string leaf_text;
   mutable int leaf_state = 0;   // 0 unknown, 1 known without a DICT atom, 2 known with one
   mutable int needs_leaf_state = 0;   // (lower.cpp needs_leaf) 0 unknown, 1 no, 2 yes
@@ -88,6 +88,13 @@ FP f_all(const std::vector<FP>& v);
 FP f_any(const std::vector<FP>& v);
 const std::string& f_to_string(const FP& f);   // (the node's cached canonical text)
 std::string spath_to_string(const SPath& p);
+// leaf-local formulas as expressions of their leaf (dexpr.hpp): which atoms can be part of one; the leaf of a leaf-local formula
+// ("" = not leaf-local; has_dict: it contains a DICT atom); its expression (throws Unsupported where it is not leaf-local)
+bool dict_foldable_atom(const Atom& a);
+std::string leaf_of(const FP& f, bool* has_dict);
+DX to_dx(const FP& f);
+// a formula that talks about the one leaf `leaf_text` (spath_to_string) as an expression of that leaf; false: it is not
+bool leaf_formula_dx(const FP& f, const std::string& leaf_text, DX* dx);
 
 // ------------------------------------------------------------------------------------------------ symbolic values
 struct SV;
@@ -110,6 +117,10 @@ struct SV {
   enum XK { XTRIM, XARR, XCOMP, XCOUNT } xkind = XTRIM;
   int idx = 0;                                    // XCOMP index / XCOUNT offset
   DX dx;                                          // DERIVED
+  // PATH / DERIVED that is ONE body's result of a function applied to one leaf (pe.cpp merge_leaf_bodies): the function's value for the
+  // leaf whichever body applies -- $pick(cond1, value1, cond2, value2 ..) -- carried through every further derivation.  Only a
+  // comparison with a value of ANOTHER leaf reads it: the function then costs one value row per side, not one per body.
+  DX pdx;
   // OPAQUE from sprintf: the HEAD of the formatted text -- literal text `hpre`, then the first verb's operand `hkey` (a review
   // leaf), then literal text `hsep` up to the next verb (`hsep_tail`: up to the END of the format) -- and a signature of format
   // and operands (`hsig`: one entry per operand, "C<json>" for constants, "P<path>" for review leaves with quantifiers erased,

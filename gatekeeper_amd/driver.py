@@ -1140,6 +1140,11 @@ class Client:
         self.driver.RemoveConstraint(c)
         self.constraints.pop((c.get("kind", ""), (c.get("metadata") or {}).get("name", "")), None)
 
+    def Dump(self):
+        """the driver's dump (frameworks Client.Dump): the compiled plan, the loaded constraints' formulas and, under
+        "value expressions:", one line per derived value row: "<leaf pattern> $v<id> = <expression>[ ordered]" """
+        return self.driver.Dump()
+
     def AddData(self, obj):
         path = process_data(obj)
         # nsCache.Add (pkg/target/ns_cache.go:23-44): a core/v1 Namespace must convert into the typed object
