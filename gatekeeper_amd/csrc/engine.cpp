@@ -295,17 +295,15 @@ struct gk_engine {
   std::mutex policy_gate;
   bool plan_dirty = true;
   uint64_t plan_gen = 0;   // bumped whenever the device plan (and with it every variant) is rebuilt
-  HostPlan fast, big;
-  DevPlan* dev_plan = nullptr;
-  std::vector<uint32_t> plan_ids;   // bitmap row -> constraint id
-  // table-specialised variants of the fast plan (GK_TABLE_RESIDENT): same formulas, element capacities = what the
+  // A plan holds a limited number of distinct violation / match formulas (one result bit each) and element scopes.  A constraint
+  // set that does not fit one plan is split into PLAN GROUPS: `groups` holds one entry per group, groups[0] the primary plan, never
+  // empty once ensure_plan has run (an empty policy set is one group without constraints).  The groups are evaluated over the same
+  // table, each into its own side of it (gk_table::Side: result buffers + path binding), and their bitmap rows are appended in list
+  // order, so callers see one [n_constraints][n_tiles] answer.  Behind unique_ptr: tables cache `const HostPlan*` into a group.
+  struct Group { HostPlan fast, big; DevPlan* dev = nullptr; std::vector<uint32_t> ids; std::vector<uint8_t> roles; };   // ids: bitmap row -> constraint id; roles: totals groups only (TR_*)
+  std::vector<std::unique_ptr<Group>> groups;
+  // table-specialised variants of a group's fast plan (GK_TABLE_RESIDENT): same formulas, element capacities = what the
   // table's largest arrays need, so the per-review LDS footprint (hence occupancy) fits the data
-  // A plan holds at most 64 distinct violation / match formulas (one result bit each) and 32 element scopes.  Larger
-  // constraint sets are split: the first group is the primary plan above, the others are evaluated one after the
-  // other over the same resident table (each on its own view: result buffers + path binding) and their bitmap rows
-  // are appended, so callers see one [n_constraints][n_tiles] answer.
-  struct Group { HostPlan fast, big; DevPlan* dev = nullptr; std::vector<uint32_t> ids; std::vector<uint8_t> roles; };   // roles: totals groups only (TR_*)
-  std::vector<std::unique_ptr<Group>> extra;
   struct Variant { HostPlan fast; DevPlan* dev = nullptr; };
   std::map<std::pair<size_t, std::vector<uint16_t>>, std::unique_ptr<Variant>> variants;   // key: (plan group, capacities)
   // plan groups (0 = the primary plan) that gk_table_verify took off the plan-specialised kernel (GK_VERIFY_QUARANTINE): every DevPlan of
@@ -341,9 +339,9 @@ struct gk_engine {
     uint32_t err_k = 0;
     // gk_resident_violations' index, kept like the err_* fields while the evaluation (vs_plan_gen) and the mask (vs_shown_gen) stand:
     // vs_prefix = exclusive prefix sum of the entries per bitmap word over ALL sources (device bits of every plan group, autoreject
-    // bits, host-evaluated violations); vs_extra = the shown slots that have an autoreject bit or a host-evaluated violation, ascending
+    // bits, host-evaluated violations); vs_host_slots = the shown slots that have an autoreject bit or a host-evaluated violation, ascending
     std::vector<uint64_t> vs_prefix;
-    std::vector<uint32_t> vs_extra;
+    std::vector<uint32_t> vs_host_slots;
     uint64_t vs_plan_gen = 0, vs_shown_gen = 0;
     gk_eval_out* ev = nullptr;        // bitmaps of the chunk's most recent evaluation
     uint64_t plan_gen = 0;            // ... and the plan generation they belong to
@@ -403,16 +401,23 @@ struct gk_table {
   uint64_t dir_bytes = 0, n_rows = 0;      // review-flag bytes (read by every launch); rows in the table
   std::vector<uint32_t> path_rows;          // rows per path: which rows a plan reads
   std::vector<uint32_t> path_max;           // per element path: largest array of one review
-  std::vector<DevTable*> views;             // one per extra plan group (shares the device arrays of `dev`)
+  // What the table keeps per plan group (gk_engine::groups), indexed like it.  sides[0] is there from the start and evaluates into the
+  // table itself; a further side is a view of the table (shares the device arrays of `dev`), made by whoever first needs it
+  // (table_sides).  Sides only grow in number and go with the table.
+  struct Side {
+    DevTable* dev = nullptr;                // what the group evaluates into: `dev` of the table (side 0) or a view of it
+    ShardInfo shard;                        // sharded sweeps: slot layout agreed with the other ranks
+    DevTable* vview = nullptr;              // the bytecode side of gk_table_verify (created by its first call)
+    DevPlan* vtwin = nullptr;               // ... and the plan it evaluates where the backend wants a plan of its own for it (dev_verify_twin;
+    uint64_t vtwin_gen = 0;                 //     nullptr on the device), of plan generation vtwin_gen
+    DevPlan* plan = nullptr;                // the plan this table runs the group on (plan_for_group), of plan generation cached_gen ...
+    const HostPlan* host = nullptr;         // ... and its host form
+  };
+  std::vector<Side> sides;
   std::vector<DevTable*> tviews;            // one per totals plan group (gk_table_totals)
-  std::vector<DevTable*> vviews;            // one per plan group: the bytecode side of gk_table_verify (created by its first call)
-  std::vector<DevPlan*> vtwins;             // ... and the plans it evaluates where the backend wants plans of its own for it (dev_verify_twin;
-  uint64_t vtwins_gen = 0;                  //     nullptr on the device), of plan generation vtwins_gen
   bool resident = false;
   bool any_prematched = false;              // some review carries RF_PREMATCHED (host.rflags says which)
-  uint64_t cached_gen = 0;                  // plan generation the cached variant choices belong to
-  std::vector<DevPlan*> cached_plan;        // per plan group (0 = the primary plan)
-  std::vector<const HostPlan*> cached_host;
+  uint64_t cached_gen = 0;                  // plan generation the sides' plan choices belong to
   std::vector<uint32_t> slot_path;          // path of each slot of the table's row-group index
   // per review: group \0 version \0 kind \0 namespace \0 name (audit order, manager.go:118-138) -- the bytes in one arena per host
   // thread's part, (offset, length) per review: a std::string per review was a malloc and a free per review
@@ -452,9 +457,7 @@ struct gk_table {
   uint64_t dict_gen = 0;                    // generation of the dictionary-predicate registry the rows were flattened under
   bool pruned = false;                      // GK_TABLE_PRUNED: rows of the registry's read set only ...
   uint64_t reads_gen = 0;                   // ... as it was when the table was built (DictRegistry::reads_gen)
-  ShardInfo shard;                          // sharded sweeps: slot layout agreed with the other ranks
-  std::vector<ShardInfo> group_shards;      // ... of the further plan groups (on their views)
-  uint64_t shard_gen = 0;
+  uint64_t shard_gen = 0;                   // plan generation the sides' shard layouts were agreed for
   gk_table_stats stats{};
 };
 
@@ -486,20 +489,54 @@ PlanCaps default_caps(const gk_engine* e) {
   return caps;
 }
 
-// Plan for one table.  Resident tables (audit sets evaluated again and again) get a variant whose element capacities
-// are what the table's largest arrays need: fewer accumulator words per review -> more tiles resident per CU, and
-// reviews that would overflow the default capacities stay on the LDS kernel.  Caller holds plan_rw (shared suffices) and variants_mu; ensure_plan ran.
-// `group`: 0 = the primary plan, g >= 1 = e->extra[g - 1] (a policy set of more than 64 formulas: round 5 -- the further groups ran
-// with the default capacities (8, 8, 8, 12, 12 -> 81 accumulator words for the 200-template corpus, whose pods hold at most 4
-// containers) until then).
-DevPlan* plan_for_group(gk_engine* e, gk_table* t, size_t group, const HostPlan** host) {
-  const HostPlan& base = group == 0 ? e->fast : e->extra[group - 1]->fast;
-  DevPlan* base_dev = group == 0 ? e->dev_plan : e->extra[group - 1]->dev;
-  *host = &base;
-  if (!t->resident || base.scopes.empty()) return base_dev;
-  if (t->cached_gen != e->plan_gen) { t->cached_plan.clear(); t->cached_host.clear(); t->cached_gen = e->plan_gen; }
-  if (t->cached_plan.size() <= group) { t->cached_plan.resize(group + 1, nullptr); t->cached_host.resize(group + 1, nullptr); }
-  if (t->cached_plan[group]) { *host = t->cached_host[group]; return t->cached_plan[group]; }   // per launch: no rescan
+// ---- plan groups: the engine's list (gk_engine::groups), a table's sides of them (gk_table::sides).  Every entry point that works
+// group by group goes through these; all of them want plan_rw held (shared suffices).
+
+// (the first group's answer is taken over as it is, the others' rows are appended)
+template <class T> void append(std::vector<T>& to, std::vector<T>&& from) {
+  if (to.empty()) to = std::move(from); else to.insert(to.end(), from.begin(), from.end());
+}
+
+// the constraint id of every bitmap row: the groups' ids in list order
+std::vector<uint32_t> all_ids(const gk_engine* e) {
+  std::vector<uint32_t> ids;
+  for (auto& g : e->groups) ids.insert(ids.end(), g->ids.begin(), g->ids.end());
+  return ids;
+}
+
+// a side of the table for every plan group there is now
+void table_sides(const gk_engine* e, gk_table* t) {
+  while (t->sides.size() < e->groups.size()) { gk_table::Side s; s.dev = dev_table_view(t->dev); t->sides.push_back(s); }
+}
+
+// One plan group as seen from one table: the engine's group `grp` (its base plan: grp.dev), the table's side of it (what it evaluates
+// into: side.dev; the plan this table runs it on, once table_plans chose it: side.plan), its number of bitmap rows and its first row
+// among all constraints.  each_group visits, in row order, the groups present on BOTH the engine and the table: a table that has not
+// been evaluated under this many groups simply lacks the later sides, the walk ends there, and the callers' size checks turn the short
+// answer into "evaluate the table first".
+struct GroupAt { size_t g; const gk_engine::Group& grp; gk_table::Side& side; uint32_t nc, row0; };
+template <class F> void each_group(const gk_engine* e, gk_table* t, F&& f) {
+  uint32_t row0 = 0;
+  for (size_t g = 0; g < e->groups.size() && g < t->sides.size(); g++) {
+    const uint32_t nc = (uint32_t)e->groups[g]->ids.size();
+    f(GroupAt{g, *e->groups[g], t->sides[g], nc, row0});
+    row0 += nc;
+  }
+}
+
+// The plan one table runs one group on, kept in the group's side while the plan generation stands (per launch: no rescan).  Resident
+// tables (audit sets evaluated again and again) get a variant whose element capacities are what the table's largest arrays need: fewer
+// accumulator words per review -> more tiles resident per CU, and reviews that would overflow the default capacities stay on the LDS
+// kernel; every group has variants of its own (key: group, capacities).  Any other table runs the group's base plan.  Caller holds
+// plan_rw (shared suffices) and variants_mu; ensure_plan and table_sides ran.
+DevPlan* plan_for_group(gk_engine* e, gk_table* t, size_t group) {
+  const gk_engine::Group& G = *e->groups[group];
+  gk_table::Side& S = t->sides[group];
+  if (t->cached_gen != e->plan_gen) { for (gk_table::Side& s : t->sides) { s.plan = nullptr; s.host = nullptr; } t->cached_gen = e->plan_gen; }
+  if (S.plan) return S.plan;
+  const HostPlan& base = G.fast;
+  S.plan = G.dev; S.host = &base;
+  if (!t->resident || base.scopes.empty()) return S.plan;
   std::vector<uint16_t> caps(base.scopes.size(), 1);
   for (size_t p = 0; p < base.ptab.size(); p++) {
     uint32_t ent = base.ptab[p];
@@ -520,23 +557,35 @@ DevPlan* plan_for_group(gk_engine* e, gk_table* t, size_t group, const HostPlan*
     std::unique_ptr<gk_engine::Variant> v(new gk_engine::Variant());
     try {
       PlanBuilder pb(&e->dict, &e->dict_reg);
-      const std::vector<uint32_t>& ids = group == 0 ? e->plan_ids : e->extra[group - 1]->ids;
-      for (uint32_t id : ids) pb.add_constraint(e->constraints[id].prep);
+      for (uint32_t id : G.ids) pb.add_constraint(e->constraints[id].prep);
       PlanCaps pc = default_caps(e);
       pc.scope_cap = caps;
       v->fast = pb.build(pc);
       if (v->fast.scopes.size() != base.scopes.size()) throw std::runtime_error("scope layout changed");
-      v->dev = dev_plan_upload(e->opts.device, v->fast, group == 0 ? e->big : e->extra[group - 1]->big);
+      v->dev = dev_plan_upload(e->opts.device, v->fast, G.big);
       if (e->quarantined.count(group)) dev_plan_no_jit(v->dev);
     } catch (const std::exception&) { v->dev = nullptr; }   // e.g. LDS limit: the default plan serves the table
     it = e->variants.emplace(key, std::move(v)).first;
   }
-  if (!it->second->dev) { t->cached_plan[group] = base_dev; t->cached_host[group] = &base; return base_dev; }
-  *host = &it->second->fast;
-  t->cached_plan[group] = it->second->dev; t->cached_host[group] = &it->second->fast;
-  return it->second->dev;
+  if (it->second->dev) { S.plan = it->second->dev; S.host = &it->second->fast; }
+  return S.plan;
 }
-DevPlan* plan_for_table(gk_engine* e, gk_table* t, const HostPlan** host) { return plan_for_group(e, t, 0, host); }
+
+// the table's side of every plan group and the plan it runs the group on: what an entry point that evaluates every group calls first
+void table_plans(gk_engine* e, gk_table* t) {
+  table_sides(e, t);
+  std::lock_guard<std::mutex> vl(e->variants_mu);
+  for (size_t g = 0; g < e->groups.size(); g++) plan_for_group(e, t, g);
+}
+
+// Why a table cannot be evaluated under the registry as it is now (nullptr: it can): rows the plans read were not made when it was flattened
+const char* table_stale(const gk_engine* e, const gk_table* t) {
+  if (t->dict_gen != e->dict_reg.gen())
+    return "the table was flattened before a constraint with dictionary predicates was added (its <leaf>.$d rows are missing): create it again";
+  if (t->pruned && t->reads_gen != e->dict_reg.reads_gen())
+    return "the pruned table was flattened before a constraint that reads other key paths was added (GK_TABLE_PRUNED): create it again";
+  return nullptr;
+}
 
 void refresh_referential(gk_engine* e);
 // The READ SET of pruned tables (GK_TABLE_PRUNED; flatten.hpp DictRegistry::set_reads): every path pattern some plan has a predicate
@@ -545,10 +594,16 @@ void refresh_referential(gk_engine* e);
 void publish_read_set(gk_engine* e) {
   std::vector<Pattern> pats;
   auto take = [&](const HostPlan& hp) { pats.insert(pats.end(), hp.pred_patterns.begin(), hp.pred_patterns.end()); };
-  take(e->fast); take(e->big);
-  for (auto& g : e->extra) { take(g->fast); take(g->big); }
+  for (auto& g : e->groups) { take(g->fast); take(g->big); }
   for (auto& c : e->constraints) if (c.alive) pats.insert(pats.end(), c.count_reads.begin(), c.count_reads.end());
   e->dict_reg.set_reads(pats);
+}
+
+// the plans are what the policy set and the path dictionary ask for (caller holds plan_rw and mu, shared suffices)
+bool plan_current(const gk_engine* e) {
+  if (e->plan_dirty || e->groups.empty() || e->groups[0]->fast.dict_size != e->dict.size()) return false;
+  for (auto& g : e->groups) if (!g->dev) return false;
+  return true;
 }
 
 void ensure_plan(gk_engine* e) {
@@ -556,35 +611,33 @@ void ensure_plan(gk_engine* e) {
   {   // the usual case: nothing changed -- decided without keeping other evaluations out
     std::shared_lock<std::shared_mutex> pl(e->plan_rw);
     std::shared_lock<std::shared_mutex> rl(e->mu);
-    if (!e->plan_dirty && e->dev_plan && e->fast.dict_size == e->dict.size()) return;
+    if (plan_current(e)) return;
   }
   std::lock_guard<std::mutex> gate(e->plan_gate);
   std::unique_lock<std::shared_mutex> l(e->plan_rw);
   std::shared_lock<std::shared_mutex> rl(e->mu);
-  if (!e->plan_dirty && e->dev_plan && e->fast.dict_size == e->dict.size()) return;
+  if (plan_current(e)) return;
   for (auto& v : e->variants) dev_plan_free(v.second->dev);
   e->variants.clear();
   PlanCaps bigcaps;
   bigcaps.level_cap[0] = bigcaps.level_cap[1] = bigcaps.level_cap[2] = 256;
-  if (e->plan_dirty || !e->dev_plan) {
-    for (auto& g : e->extra) dev_plan_free(g->dev);
-    e->extra.clear();
-    e->quarantined.clear();   // (new plans, new generated text: specialised afresh, to be verified afresh)
+  if (e->plan_dirty || e->groups.empty()) {
     std::vector<const ConstraintRec*> alive;
     for (auto& c : e->constraints) if (c.alive) alive.push_back(&c);
     for (auto* c : alive) if (!c->broken.empty()) throw Unsupported(c->broken);   // (a referential constraint the current inventory does not compile for)
     // groups of constraints that fit one plan: everything if possible, else chunks of <= GK_MAX_VIOL constraints (a constraint
-    // contributes one violation and one match formula), halved further while a chunk still does not lower
-    std::vector<std::vector<const ConstraintRec*>> groups;
-    auto builds = [&](const std::vector<const ConstraintRec*>& g, HostPlan* fast, HostPlan* big) {
+    // contributes one violation and one match formula), halved further while a chunk still does not lower.  The new list replaces the
+    // old one when all of it is built.
+    std::vector<std::unique_ptr<gk_engine::Group>> next;
+    auto build = [&](const std::vector<const ConstraintRec*>& g) {
+      std::unique_ptr<gk_engine::Group> grp(new gk_engine::Group());
       PlanBuilder pb(&e->dict, &e->dict_reg);
-      for (auto* c : g) pb.add_constraint(c->prep);
-      *fast = pb.build(default_caps(e));
-      *big = pb.build(bigcaps);
+      for (auto* c : g) { pb.add_constraint(c->prep); grp->ids.push_back(c->id); }
+      grp->fast = pb.build(default_caps(e));
+      grp->big = pb.build(bigcaps);
+      next.push_back(std::move(grp));
     };
-    std::vector<std::pair<HostPlan, HostPlan>> plans;
     std::function<void(const std::vector<const ConstraintRec*>&)> place = [&](const std::vector<const ConstraintRec*>& g) {
-      HostPlan f, b;
       // (test / tuning aid, gk_debug_set("group_max", n): no plan group of more than n constraints -- the several-group machinery,
       //  which a set of more than 256 distinct violation formulas still takes, stays testable with a small corpus)
       if (const int forced = g_debug_group_max.load(); forced > 0 && g.size() > (size_t)forced) {
@@ -592,7 +645,7 @@ void ensure_plan(gk_engine* e) {
           place(std::vector<const ConstraintRec*>(g.begin() + i, g.begin() + std::min(g.size(), i + (size_t)forced)));
         return;
       }
-      try { builds(g, &f, &b); }
+      try { build(g); }
       catch (const Unsupported& u) {
         if (g.size() == 1 && g[0]->referential)   // (its formula follows the synced objects: say so -- the same words refresh_referential uses)
           throw Unsupported(std::string("referential constraint ") + g[0]->kind + "/" + g[0]->name + " does not compile against the synced inventory: " + u.what());
@@ -602,29 +655,16 @@ void ensure_plan(gk_engine* e) {
         size_t half = g.size() > cap ? cap : g.size() / 2;
         for (size_t i = 0; i < g.size(); i += half)
           place(std::vector<const ConstraintRec*>(g.begin() + i, g.begin() + std::min(g.size(), i + half)));
-        return;
       }
-      groups.push_back(g);
-      plans.emplace_back(std::move(f), std::move(b));
     };
     place(alive);
-    e->plan_ids.clear();
-    if (groups.empty()) { groups.emplace_back(); HostPlan f, b; builds(groups[0], &f, &b); plans.emplace_back(std::move(f), std::move(b)); }
-    for (auto* c : groups[0]) e->plan_ids.push_back(c->id);
-    e->fast = std::move(plans[0].first);
-    e->big = std::move(plans[0].second);
-    for (size_t gi = 1; gi < groups.size(); gi++) {
-      std::unique_ptr<gk_engine::Group> g(new gk_engine::Group());
-      g->fast = std::move(plans[gi].first);
-      g->big = std::move(plans[gi].second);
-      for (auto* c : groups[gi]) g->ids.push_back(c->id);
-      e->extra.push_back(std::move(g));
-    }
+    if (next.empty()) build({});   // (an empty policy set: one group without constraints)
+    for (auto& g : e->groups) dev_plan_free(g->dev);
+    e->groups = std::move(next);
+    e->quarantined.clear();   // (new plans, new generated text: specialised afresh, to be verified afresh)
   } else {
     try {
-      e->fast.resolve_paths(e->dict);
-      e->big.resolve_paths(e->dict);
-      for (auto& g : e->extra) { g->fast.resolve_paths(e->dict); g->big.resolve_paths(e->dict); }
+      for (auto& g : e->groups) { g->fast.resolve_paths(e->dict); g->big.resolve_paths(e->dict); }
     } catch (const Unsupported& u) {
       // the plan was built before the table's key paths were known and does not fit them: with a referential constraint loaded
       // that is its unrolled inventory (one predicate per synced value on the joined path) -- say so
@@ -633,13 +673,11 @@ void ensure_plan(gk_engine* e) {
       throw;
     }
   }
-  for (auto& g : e->extra) {
+  for (auto& g : e->groups) {
     if (g->dev) { dev_plan_free(g->dev); g->dev = nullptr; }
     g->dev = dev_plan_upload(e->opts.device, g->fast, g->big);
   }
-  if (e->dev_plan) { dev_plan_free(e->dev_plan); e->dev_plan = nullptr; }
-  e->dev_plan = dev_plan_upload(e->opts.device, e->fast, e->big);
-  for (size_t g : e->quarantined) if (DevPlan* p = g == 0 ? e->dev_plan : g - 1 < e->extra.size() ? e->extra[g - 1]->dev : nullptr) dev_plan_no_jit(p);
+  for (size_t g : e->quarantined) if (g < e->groups.size()) dev_plan_no_jit(e->groups[g]->dev);
   e->plan_gen++;
   e->plan_dirty = false;
   publish_read_set(e);
@@ -956,9 +994,8 @@ void gk_engine_destroy(gk_engine* e) {
   dev_jit_quiesce();   // background builds of this engine's plans (a host that destroys its engines before exit() never exits under a running compile)
   if (e->comm) dev_comm_free(e->comm);
   for (auto& c : e->resident.chunks) { if (c.ev) gk_eval_free(c.ev); if (c.table) gk_table_free(c.table); }
-  if (e->dev_plan) dev_plan_free(e->dev_plan);
   for (auto& v : e->variants) dev_plan_free(v.second->dev);
-  for (auto& g : e->extra) dev_plan_free(g->dev);
+  for (auto& g : e->groups) dev_plan_free(g->dev);
   for (auto& g : e->totals_groups) dev_plan_free(g->dev);
   delete e;
 }
@@ -1318,7 +1355,7 @@ static int table_create_impl(gk_engine* e, const gk_review_in* reviews, size_t n
       try {
         ensure_plan(e);
         std::shared_lock<std::shared_mutex> pl(e->plan_rw);
-        if (!e->extra.empty() || (size_t)e->fast.dims.acc_words * 256 * 4 > 72 * 1024) rpt = 128;
+        if (e->groups.size() > 1 || (size_t)e->groups[0]->fast.dims.acc_words * 256 * 4 > 72 * 1024) rpt = 128;
       } catch (const std::exception&) {}
     }
     if (const char* rp = getenv("GK_RPT")) { int v = atoi(rp); if (v == 64 || v == 128 || v == 256 || v == 512) rpt = (uint32_t)v; }
@@ -1539,6 +1576,8 @@ static int table_create_impl(gk_engine* e, const gk_review_in* reviews, size_t n
     }
     const auto t_indexed = std::chrono::steady_clock::now();
     t->dev = dev_table_assemble(e->opts.device, dev_parts, t->host);
+    t->sides.emplace_back();
+    t->sides[0].dev = t->dev;
     const auto t_up = std::chrono::steady_clock::now();
     t->n_reviews = (uint32_t)n;
     t->dir_bytes = t->host.rflags.size() * 4;
@@ -1670,13 +1709,14 @@ int gk_table_get_stats(const gk_table* t, gk_table_stats* out) {
 
 void gk_table_free(gk_table* t) {
   if (!t) return;
-  for (DevTable* v : t->views) dev_table_free(v);
   for (DevTable* v : t->tviews) dev_table_free(v);
-  for (DevTable* v : t->views) dev_verify_forget(v);
-  for (DevTable* v : t->vviews) { dev_verify_forget(v); dev_table_free(v); }
-  for (DevPlan* p : t->vtwins) dev_plan_free(p);
-  dev_verify_forget(t->dev);
-  dev_table_free(t->dev);
+  for (size_t g = t->sides.size(); g-- > 0;) {   // (views before the table: side 0 last)
+    gk_table::Side& s = t->sides[g];
+    if (s.vview) { dev_verify_forget(s.vview); dev_table_free(s.vview); }
+    dev_plan_free(s.vtwin);
+    dev_verify_forget(s.dev);
+    dev_table_free(s.dev);
+  }
   delete t;
 }
 
@@ -1693,10 +1733,7 @@ int gk_table_eval(gk_engine* e, gk_table* t, uint32_t flags, gk_eval_out** out) 
   if (!e || !t || !out) return fail(GK_ERR_INVALID, "NULL argument");
   try {
     ensure_plan(e);
-    if (t->dict_gen != e->dict_reg.gen())
-      return fail(GK_ERR_INVALID, "the table was flattened before a constraint with dictionary predicates was added (its <leaf>.$d rows are missing): create it again");
-    if (t->pruned && t->reads_gen != e->dict_reg.reads_gen())
-      return fail(GK_ERR_INVALID, "the pruned table was flattened before a constraint that reads other key paths was added (GK_TABLE_PRUNED): create it again");
+    if (const char* why = table_stale(e, t)) return fail(GK_ERR_INVALID, why);
     std::unique_ptr<EvalHolder> h(new EvalHolder());
     EvalOptions opt;
     opt.download = !(flags & GK_EVAL_NO_DOWNLOAD);
@@ -1711,34 +1748,27 @@ int gk_table_eval(gk_engine* e, gk_table* t, uint32_t flags, gk_eval_out** out) 
     {
       { std::lock_guard<std::mutex> gate(e->plan_gate); }   // (a plan change that is waiting goes first)
       std::shared_lock<std::shared_mutex> l(e->plan_rw);
-      h->ids = e->plan_ids;
+      h->ids = all_ids(e);
       if (flags & GK_EVAL_WANT_LIST) opt.list_capacity = std::max<uint32_t>(1024, t->n_reviews * 4u);
-      const HostPlan* hp = nullptr;
-      DevPlan* dp = nullptr;
-      { std::lock_guard<std::mutex> vl(e->variants_mu); dp = plan_for_table(e, t, &hp); }
-      while (t->views.size() < e->extra.size()) t->views.push_back(dev_table_view(t->dev));
-      std::vector<DevPlan*> gdev(e->extra.size(), nullptr);   // the further plan groups: table-sized variants as well
-      { std::lock_guard<std::mutex> vl(e->variants_mu); for (size_t gi = 0; gi < e->extra.size(); gi++) { const HostPlan* gh = nullptr; gdev[gi] = plan_for_group(e, t, gi + 1, &gh); } }
-      // every plan group is LAUNCHED before any is collected: the groups work on their own streams (views of the table) and
+      table_plans(e, t);   // every plan group: its side of the table, its table-sized variant
+      // every plan group is LAUNCHED before any is collected: the groups work on their own streams (sides of the table) and
       // overlap on the device as far as their footprints allow
       if (!(flags & GK_EVAL_COLLECT)) {
         // (several plan groups: their plan-specialised builds are all started first and compile side by side)
-        if (!e->extra.empty() && opt.jit_wait) { dev_jit_prefetch(dp, t->dev); for (size_t gi = 0; gi < e->extra.size(); gi++) dev_jit_prefetch(gdev[gi], t->views[gi]); }
-        dev_eval_launch(dp, t->dev, opt);
-        for (size_t gi = 0; gi < e->extra.size(); gi++) dev_eval_launch(gdev[gi], t->views[gi], opt);
+        if (e->groups.size() > 1 && opt.jit_wait) each_group(e, t, [&](const GroupAt& g) { dev_jit_prefetch(g.side.plan, g.side.dev); });
+        each_group(e, t, [&](const GroupAt& g) { dev_eval_launch(g.side.plan, g.side.dev, opt); });
       }
       if (flags & GK_EVAL_ASYNC) {   // enqueue only; a later call without GK_EVAL_ASYNC collects
         *out = nullptr;
         return GK_OK;
       }
-      dev_eval_finish(dp, t->dev, opt, &h->out);
-      h->lds_bytes = h->out.lds_bytes;
-      // further plan groups: same table, their rows are appended below the primary group's
-      for (size_t gi = 0; gi < e->extra.size(); gi++) {
-        EvalOut og;
-        dev_eval_finish(gdev[gi], t->views[gi], opt, &og);
-        const uint32_t row_base = h->out.n_constraints;
+      // collected in group order: the primary group's answer is the call's, the rows of every further group are appended below it
+      each_group(e, t, [&](const GroupAt& g) {
         EvalOut& o = h->out;
+        if (g.g == 0) { dev_eval_finish(g.side.plan, g.side.dev, opt, &o); h->lds_bytes = o.lds_bytes; return; }
+        EvalOut og;
+        dev_eval_finish(g.side.plan, g.side.dev, opt, &og);
+        const uint32_t row_base = o.n_constraints;
         o.viol.insert(o.viol.end(), og.viol.begin(), og.viol.end());
         o.err.insert(o.err.end(), og.err.begin(), og.err.end());
         o.match.insert(o.match.end(), og.match.begin(), og.match.end());
@@ -1753,8 +1783,7 @@ int gk_table_eval(gk_engine* e, gk_table* t, uint32_t flags, gk_eval_out** out) 
         o.kernel_hash = o.kernel_hash * 1099511628211ull ^ og.kernel_hash;   // (several plan groups: one figure that names all their texts)
         o.n_constraints += og.n_constraints;
         o.d_viol = o.d_err = o.d_counts = nullptr;   // not one contiguous device buffer any more
-        h->ids.insert(h->ids.end(), e->extra[gi]->ids.begin(), e->extra[gi]->ids.end());
-      }
+      });
     }
     // reviews the device could not evaluate (too_big) are answered by the engine's own exact evaluator where their text is at hand
     if (opt.download && !(flags & GK_EVAL_DEVICE_ONLY)) complete_on_host(e, t, h.get(), opt.want_match, (flags & GK_EVAL_WANT_LIST) != 0);
@@ -1801,10 +1830,11 @@ int gk_table_eval(gk_engine* e, gk_table* t, uint32_t flags, gk_eval_out** out) 
       }
       plan_bytes += (uint64_t)hp.path_preds.size() * sizeof(Pred) + hp.code.size() * 4 + hp.cheap.size();
     };
+    size_t n_groups = 0;
     {
       std::shared_lock<std::shared_mutex> l(e->plan_rw);
-      account(e->fast);
-      for (auto& g : e->extra) account(g->fast);
+      for (auto& g : e->groups) account(g->fast);
+      n_groups = e->groups.size();
     }
     // (review words, review_words.hpp: a sweep whose binding evaluated the all-global classes once streams their words -- 4 B per word
     //  and review, padded to 64 reviews -- instead of their rows; the one-off binding pass is not a per-sweep figure)
@@ -1812,13 +1842,13 @@ int gk_table_eval(gk_engine* e, gk_table* t, uint32_t flags, gk_eval_out** out) 
     rows_read -= rw_rows; hdrs_read -= rw_hdrs;
     // (the once-per-table figures: with one plan group a hoisted slot is not streamed at all; with several, a slot hoisted by one group
     //  may be kept by another, which the sums cannot tell -- the figure then stays the upper bound)
-    if (e->extra.empty()) { rows_once -= std::min(rows_once, rw_rows); hdrs_once -= std::min(hdrs_once, rw_hdrs); }
+    if (n_groups == 1) { rows_once -= std::min(rows_once, rw_rows); hdrs_once -= std::min(hdrs_once, rw_hdrs); }
     p.n_rows_read = rows_read;
     (void)bound;
     p.algo_bytes = rows_read * sizeof(Row) + hdrs_read * sizeof(StrHdr) + h->out.list_bytes + h->out.rw_bytes +
-                   t->dir_bytes * (1 + e->extra.size()) + plan_bytes + (uint64_t)p.n_constraints * p.n_tiles * 16 + (uint64_t)p.list_total * 8;
-    p.algo_bytes_once = p.algo_bytes - (rows_read - rows_once) * sizeof(Row) - (hdrs_read - hdrs_once) * sizeof(StrHdr) - t->dir_bytes * e->extra.size();
-    p.n_plan_groups = 1 + (uint32_t)e->extra.size();
+                   t->dir_bytes * n_groups + plan_bytes + (uint64_t)p.n_constraints * p.n_tiles * 16 + (uint64_t)p.list_total * 8;
+    p.algo_bytes_once = p.algo_bytes - (rows_read - rows_once) * sizeof(Row) - (hdrs_read - hdrs_once) * sizeof(StrHdr) - t->dir_bytes * (n_groups - 1);   // (the review flags once, not per group)
+    p.n_plan_groups = (uint32_t)n_groups;
     *out = &h.release()->pub;
     return GK_OK;
   } catch (const Unsupported& ex) { return fail(GK_ERR_UNSUPPORTED, ex.what());
@@ -1855,15 +1885,11 @@ int gk_table_topk(gk_engine* e, gk_table* t, uint32_t k, gk_topk_out** out) {
     h->ids = t->last_ids;
     {
       std::shared_lock<std::shared_mutex> l(e->plan_rw);
-      const uint32_t nc0 = (uint32_t)e->plan_ids.size();
-      dev_topk(t->dev, nc0, t->order, t->grp, k, cap, &h->reviews, &h->counts, &h->overflow);
-      for (size_t gi = 0; gi < e->extra.size() && gi < t->views.size(); gi++) {   // further plan groups: rows appended
+      each_group(e, t, [&](const GroupAt& g) {   // the groups' rows, appended
         std::vector<uint32_t> r, c, o;
-        dev_topk(t->views[gi], (uint32_t)e->extra[gi]->ids.size(), t->order, t->grp, k, cap, &r, &c, &o);
-        h->reviews.insert(h->reviews.end(), r.begin(), r.end());
-        h->counts.insert(h->counts.end(), c.begin(), c.end());
-        h->overflow.insert(h->overflow.end(), o.begin(), o.end());
-      }
+        dev_topk(g.side.dev, g.nc, t->order, t->grp, k, cap, &r, &c, &o);
+        append(h->reviews, std::move(r)); append(h->counts, std::move(c)); append(h->overflow, std::move(o));
+      });
     }
     // (violating pairs the host evaluation of the last gk_table_eval added are no part of the device bitmaps: they join the candidates
     //  -- a candidate too many costs a rendering, the host sorts and cuts the lists anyway; a full row says "walk the bitmap row")
@@ -2067,8 +2093,7 @@ static std::vector<uint64_t> render_needed(gk_engine* e, gk_table* t, const std:
   std::vector<uint64_t> need = viol;
   counted->assign(ids.size(), 0); sum->assign(ids.size(), 0);
   if (getenv("GK_TOTALS_RENDER_ALL") || t->n_reviews == 0) return need;
-  if (t->dict_gen != e->dict_reg.gen()) return need;   // (a table flattened before the constraint set changed: no totals plan can read it)
-  if (t->pruned && t->reads_gen != e->dict_reg.reads_gen()) return need;
+  if (table_stale(e, t)) return need;   // (a table flattened before the constraint set changed: no totals plan can read it)
   std::lock_guard<std::mutex> tl(e->totals_mu);
   ensure_totals_plans(e);
   if (e->totals_groups.empty()) return need;
@@ -2165,12 +2190,11 @@ int gk_table_totals(gk_engine* e, gk_table* t, gk_totals_out** out) {
     std::vector<uint64_t> viol;
     {
       std::shared_lock<std::shared_mutex> l(e->plan_rw);
-      dev_last_viol(t->dev, (uint32_t)e->plan_ids.size(), &viol);
-      for (size_t gi = 0; gi < e->extra.size() && gi < t->views.size(); gi++) {
+      each_group(e, t, [&](const GroupAt& g) {
         std::vector<uint64_t> v;
-        dev_last_viol(t->views[gi], (uint32_t)e->extra[gi]->ids.size(), &v);
-        viol.insert(viol.end(), v.begin(), v.end());
-      }
+        dev_last_viol(g.side.dev, g.nc, &v);
+        append(viol, std::move(v));
+      });
     }
     if (viol.size() != (size_t)nc * nt) return fail(GK_ERR_INVALID, "gk_table_totals: evaluate the table first");
     h->results.assign(nc, 0); h->pairs.assign(nc, 0);
@@ -2466,21 +2490,17 @@ int gk_table_sweep_sharded(gk_engine* e, gk_table* t, uint32_t flags, gk_shard_o
   if (!e->comm) return fail(GK_ERR_INVALID, "gk_comm_init first");
   try {
     ensure_plan(e);
-    if (t->dict_gen != e->dict_reg.gen()) return fail(GK_ERR_INVALID, "the table was flattened before a constraint with dictionary predicates was added: create it again");
-    if (t->pruned && t->reads_gen != e->dict_reg.reads_gen())
-      return fail(GK_ERR_INVALID, "the pruned table was flattened before a constraint that reads other key paths was added (GK_TABLE_PRUNED): create it again");
+    if (const char* why = table_stale(e, t)) return fail(GK_ERR_INVALID, why);
     std::unique_ptr<ShardHolder> h(new ShardHolder());
     std::shared_lock<std::shared_mutex> l(e->plan_rw);
-    const HostPlan* hp = nullptr;
-    DevPlan* dp = nullptr;
-    { std::lock_guard<std::mutex> vl(e->variants_mu); dp = plan_for_table(e, t, &hp); }
-    const uint32_t nc0 = (uint32_t)e->plan_ids.size();
-    const size_t n_groups = 1 + e->extra.size();
-    while (t->views.size() < e->extra.size()) t->views.push_back(dev_table_view(t->dev));
-    if (t->shard_gen != e->plan_gen || t->shard.shard_reviews.empty() || t->group_shards.size() != e->extra.size()) {   // (collective) once per table and plan
-      dev_shard_setup(t->dev, e->comm, nc0, &t->shard);
-      t->group_shards.assign(e->extra.size(), ShardInfo());
-      for (size_t gi = 0; gi < e->extra.size(); gi++) dev_shard_setup(t->views[gi], e->comm, (uint32_t)e->extra[gi]->ids.size(), &t->group_shards[gi]);
+    table_sides(e, t);
+    { std::lock_guard<std::mutex> vl(e->variants_mu); plan_for_group(e, t, 0); }
+    // (here only the primary group runs its table-sized variant; the further groups run their base plans)
+    auto plan_of = [](const GroupAt& g) { const DevPlan* p = g.grp.dev; if (g.g == 0) p = g.side.plan; return p; };
+    const size_t n_groups = e->groups.size();
+    const ShardInfo& shard0 = t->sides[0].shard;
+    if (t->shard_gen != e->plan_gen || shard0.shard_reviews.empty()) {   // (collective) once per table and plan
+      each_group(e, t, [&](const GroupAt& g) { dev_shard_setup(g.side.dev, e->comm, g.nc, &g.side.shard); });
       t->shard_gen = e->plan_gen;
     }
     EvalOptions opt;
@@ -2495,98 +2515,78 @@ int gk_table_sweep_sharded(gk_engine* e, gk_table* t, uint32_t flags, gk_shard_o
     const uint64_t rejected = t->n_rejected;
     if (enqueue) {   // sweep + exchange of every plan group onto the stream(s); whoever collects waits for them
       // (four enqueues per plan group; GK_SHARD_GRAPH=1: a single plan group's step replays as one captured graph)
-      dev_shard_enqueue(dp, t->dev, e->comm, opt, nc0, rejected, e->extra.empty());
-      for (size_t gi = 0; gi < e->extra.size(); gi++)
-        dev_shard_enqueue(e->extra[gi]->dev, t->views[gi], e->comm, opt, (uint32_t)e->extra[gi]->ids.size(), rejected, false);
+      each_group(e, t, [&](const GroupAt& g) { dev_shard_enqueue(plan_of(g), g.side.dev, e->comm, opt, g.nc, rejected, n_groups == 1); });
       if (out) *out = nullptr;
       return GK_OK;
     }
+    // Per plan group: the local evaluation, finished (incl. the large-capacity pass for overflowing reviews) BEFORE the exchange, so
+    // that the gathered bitmaps are complete; then the exchange step on the same stream (each group has its own slot buffer on its
+    // side of the table).  GK_SHARD_COLLECT, one plan group only: the answer of the last enqueue-only pass, without sweeping again --
+    // unless some review of that pass, on any rank, was left to the large-capacity re-run (then this is an ordinary collecting sweep;
+    // every rank decides alike).
+    // What the bitmaps cannot say travels with the totals (fail closed, like Client.AuditAggregate): autoreject pairs, reviews
+    // beyond the engine's limits, reviews HandleReview rejected when this shard was built
     EvalOut eo;
-    // local evaluation, finished (incl. the large-capacity pass for overflowing reviews) BEFORE the exchange, so that the
-    // gathered bitmaps are complete; then the exchange step on the same stream.  A constraint set that needs several
-    // plan groups runs one evaluation + exchange per group (each group has its own slot buffer on its view of the table).
     const void* d_all = nullptr;
     const bool want_host = (flags & GK_SHARD_DOWNLOAD) != 0;
-    std::vector<uint64_t> g0;
-    // GK_SHARD_COLLECT: the answer of the last enqueue-only pass, without sweeping again -- unless some review of that pass,
-    // on any rank, was left to the large-capacity re-run (then this is an ordinary collecting sweep; every rank decides alike)
-    const bool collected = (flags & GK_SHARD_COLLECT) && e->extra.empty() &&
-                           dev_shard_collect(t->dev, e->comm, nc0, &h->totals, want_host ? &g0 : nullptr, &d_all);
-    if (!collected) dev_eval(dp, t->dev, opt, &eo);
-    // what the bitmaps cannot say travels with the totals (fail closed, like Client.AuditAggregate): autoreject pairs, reviews
-    // beyond the engine's limits, reviews HandleReview rejected when this shard was built
+    std::vector<std::vector<uint64_t>> parts(n_groups);   // the groups' gathered slots (host copies)
     int64_t beyond = 0, not_eval = 0;
-    auto split = [&](std::vector<int64_t>& raw, uint32_t ncg, bool first) {   // raw: [ncg] pairs | [ncg] autoreject | beyond | not evaluated | left to the re-run
-      h->err_totals.insert(h->err_totals.end(), raw.begin() + ncg, raw.begin() + 2 * (size_t)ncg);
-      beyond += raw[2 * (size_t)ncg];
-      if (first) not_eval = raw[2 * (size_t)ncg + 1];
-      raw.resize(ncg);
-    };
-    if (!collected) dev_shard_exchange(t->dev, e->comm, nc0, rejected, &h->totals, want_host ? &g0 : nullptr, &d_all);
-    split(h->totals, nc0, true);
-    uint32_t nc = nc0;
-    if (n_groups == 1) h->gathered.swap(g0);
-    else {
-      // merged view for the caller: per rank [all groups' bitmap rows | all groups' counts], same stride; host copy only
-      const int world = dev_comm_world(e->comm);
-      const uint32_t stride = t->shard.stride_tiles;
-      std::vector<std::vector<uint64_t>> parts(n_groups);
-      std::vector<uint32_t> ncs{nc0};
-      std::vector<uint64_t> slot_bytes{t->shard.slot_bytes};
-      parts[0].swap(g0);
-      for (size_t gi = 0; gi < e->extra.size(); gi++) {
+    uint32_t nc = 0;
+    bool collected = false;
+    each_group(e, t, [&](const GroupAt& g) {
+      std::vector<int64_t> raw;   // [nc] pairs | [nc] autoreject | beyond | not evaluated | left to the re-run
+      std::vector<uint64_t>* host = want_host ? &parts[g.g] : nullptr;
+      if ((flags & GK_SHARD_COLLECT) && n_groups == 1) collected = dev_shard_collect(g.side.dev, e->comm, g.nc, &raw, host, &d_all);
+      if (!collected) {
         EvalOut og;
-        dev_eval(e->extra[gi]->dev, t->views[gi], opt, &og);
+        dev_eval(plan_of(g), g.side.dev, opt, &og);
         eo.kernel_ms += og.kernel_ms; eo.fast_kernel_ms += og.fast_kernel_ms; eo.n_overflow += og.n_overflow;
-        std::vector<int64_t> tg;
-        const void* d_g = nullptr;
-        const uint32_t ncg = (uint32_t)e->extra[gi]->ids.size();
-        dev_shard_exchange(t->views[gi], e->comm, ncg, rejected, &tg, want_host ? &parts[gi + 1] : nullptr, &d_g);
-        split(tg, ncg, false);
-        h->totals.insert(h->totals.end(), tg.begin(), tg.end());
-        ncs.push_back(ncg); slot_bytes.push_back(t->group_shards[gi].slot_bytes);
-        nc += ncg;
+        dev_shard_exchange(g.side.dev, e->comm, g.nc, rejected, &raw, host, &d_all);
       }
+      h->err_totals.insert(h->err_totals.end(), raw.begin() + g.nc, raw.begin() + 2 * (size_t)g.nc);
+      beyond += raw[2 * (size_t)g.nc];
+      if (g.g == 0) not_eval = raw[2 * (size_t)g.nc + 1];
+      h->totals.insert(h->totals.end(), raw.begin(), raw.begin() + g.nc);
+      nc += g.nc;
+    });
+    if (n_groups == 1) h->gathered.swap(parts[0]);
+    else {
       d_all = nullptr;   // several device buffers: only the merged host copy is handed out
       if (want_host) {
+        // merged view for the caller: per rank [all groups' bitmap rows | all groups' counts], same stride; host copy only
+        const int world = dev_comm_world(e->comm);
+        const uint32_t stride = shard0.stride_tiles;
         const uint64_t merged_slot = (((uint64_t)nc * stride * 8 + (uint64_t)nc * 4) + 15) & ~(uint64_t)15;
         h->gathered.assign((size_t)world * merged_slot / 8, 0);
         for (int r = 0; r < world; r++) {
           uint8_t* dst = reinterpret_cast<uint8_t*>(h->gathered.data()) + (size_t)r * merged_slot;
-          size_t row0 = 0;
-          for (size_t g = 0; g < n_groups; g++) {
-            const uint8_t* src = reinterpret_cast<const uint8_t*>(parts[g].data()) + (size_t)r * slot_bytes[g];
-            memcpy(dst + row0 * stride * 8, src, (size_t)ncs[g] * stride * 8);
-            memcpy(dst + (size_t)nc * stride * 8 + row0 * 4, src + (size_t)ncs[g] * stride * 8, (size_t)ncs[g] * 4);
-            row0 += ncs[g];
-          }
+          each_group(e, t, [&](const GroupAt& g) {
+            const uint8_t* src = reinterpret_cast<const uint8_t*>(parts[g.g].data()) + (size_t)r * g.side.shard.slot_bytes;
+            memcpy(dst + (size_t)g.row0 * stride * 8, src, (size_t)g.nc * stride * 8);
+            memcpy(dst + (size_t)nc * stride * 8 + (size_t)g.row0 * 4, src + (size_t)g.nc * stride * 8, (size_t)g.nc * 4);
+          });
         }
         h->merged_slot = merged_slot;
       }
     }
-    h->ids = e->plan_ids;
-    for (auto& g : e->extra) h->ids.insert(h->ids.end(), g->ids.begin(), g->ids.end());
-    h->shard_reviews = t->shard.shard_reviews;
+    h->ids = all_ids(e);
+    h->shard_reviews = shard0.shard_reviews;
     gk_shard_out& p = h->pub;
     memset(&p, 0, sizeof p);
     p.world = (uint32_t)dev_comm_world(e->comm); p.rank = (uint32_t)dev_comm_rank(e->comm);
-    p.n_constraints = nc; p.stride_tiles = t->shard.stride_tiles; p.slot_bytes = n_groups == 1 ? t->shard.slot_bytes : h->merged_slot;
+    p.n_constraints = nc; p.stride_tiles = shard0.stride_tiles; p.slot_bytes = n_groups == 1 ? shard0.slot_bytes : h->merged_slot;
     p.constraint_ids = h->ids.data(); p.shard_reviews = h->shard_reviews.data(); p.totals = h->totals.data();
     p.gathered = h->gathered.empty() ? nullptr : h->gathered.data();
     p.d_gathered = d_all;
     p.kernel_ms = eo.kernel_ms; p.fast_kernel_ms = eo.fast_kernel_ms; p.n_overflow = eo.n_overflow;
     p.err_totals = h->err_totals.data(); p.beyond_limits = beyond; p.not_evaluated = not_eval;
-    {   // the exchange step's own figures (the primary plan group's; further groups exchange the same number of bytes per row)
-      const ShardExchangeStats xs = dev_shard_exchange_stats(t->dev, e->comm);
-      p.exchange_ms = collected ? 0.f : xs.exchange_ms;   // (a collected enqueue-only pass was not timed)
-      p.exchange_bytes_inbound = xs.inbound_bytes;
-      for (size_t gi = 0; gi < e->extra.size() && gi < t->views.size(); gi++) {
-        const ShardExchangeStats xg = dev_shard_exchange_stats(t->views[gi], e->comm);
-        if (!collected) p.exchange_ms += xg.exchange_ms;
-        p.exchange_bytes_inbound += xg.inbound_bytes;
-      }
-      p.exchange_overlapped = xs.overlap ? 1u : 0u;
-    }
+    // the exchange step's own figures: time and bytes of every group (a collected enqueue-only pass was not timed), overlap as the primary group says
+    each_group(e, t, [&](const GroupAt& g) {
+      const ShardExchangeStats xs = dev_shard_exchange_stats(g.side.dev, e->comm);
+      if (!collected) p.exchange_ms += xs.exchange_ms;
+      p.exchange_bytes_inbound += xs.inbound_bytes;
+      if (g.g == 0) p.exchange_overlapped = xs.overlap ? 1u : 0u;
+    });
     *out = &h.release()->pub;
     return GK_OK;
   } catch (const Unsupported& ex) { return fail(GK_ERR_UNSUPPORTED, ex.what());
@@ -2644,7 +2644,7 @@ static int resident_update(gk_engine* e, uint64_t* flattened_out, std::chrono::s
   // compaction: when masked-out slots outnumber the live ones (or the chunks have piled up) everything is flattened
   // again into one chunk
   bool stale_rows = false;   // a constraint with dictionary predicates arrived: every chunk lacks its <leaf>.$d rows
-  for (auto& c : R.chunks) stale_rows = stale_rows || c.table->dict_gen != e->dict_reg.gen() || (c.table->pruned && c.table->reads_gen != e->dict_reg.reads_gen());
+  for (auto& c : R.chunks) stale_rows = stale_rows || table_stale(e, c.table);
   if (stale_rows || R.n_dead_slots > R.n_live + 1024 || R.chunks.size() > 16) {
     for (auto& c : R.chunks) resident_drop_chunk(c);
     R.chunks.clear();
@@ -2716,10 +2716,24 @@ static int resident_update(gk_engine* e, uint64_t* flattened_out, std::chrono::s
   } else {
     { std::lock_guard<std::mutex> gate(e->plan_gate); }   // (a plan change that is waiting goes first)
     std::shared_lock<std::shared_mutex> l(e->plan_rw);
-    *ids = e->plan_ids;
-    for (auto& g : e->extra) ids->insert(ids->end(), g->ids.begin(), g->ids.end());
+    *ids = all_ids(e);
   }
   return GK_OK;
+}
+
+// shown reviews of a chunk that its evaluation left beyond the device's limits
+static uint64_t shown_beyond(const gk_engine::ResChunk& c) {
+  uint64_t n = 0;
+  for (uint32_t w = 0; w < c.ev->n_tiles && w < c.shown.size(); w++) n += (uint64_t)__builtin_popcountll(c.ev->too_big[w] & c.shown[w]);
+  return n;
+}
+
+// a resident object's inventory path as a JSON array, appended to `out`
+static void append_path_json(const std::vector<std::string>& path, std::string& out) {
+  out += '[';
+  bool first = true;
+  for (const std::string& seg : path) { if (!first) out += ','; first = false; json_escape(seg, out); }
+  out += ']';
 }
 
 // results, not pairs (pkg/audit/manager.go:902), over the shown slots of all chunks (R.mu held by the caller)
@@ -2779,7 +2793,7 @@ int gk_resident_sweep(gk_engine* e, uint32_t flags, gk_sweep_out** out) {
       const gk_eval_out* ev = c.ev;
       for (uint32_t row = 0; row < ev->n_constraints && row < nc; row++)
         for (uint32_t w = 0; w < ev->n_tiles; w++) h->pairs[row] += (uint64_t)__builtin_popcountll(ev->viol[(size_t)row * ev->n_tiles + w] & c.shown[w]);
-      for (uint32_t w = 0; w < ev->n_tiles; w++) beyond += (uint64_t)__builtin_popcountll(ev->too_big[w] & c.shown[w]);
+      beyond += shown_beyond(c);
     }
     if (flags & GK_SWEEP_RESULT_TOTALS) resident_result_totals(e, h->ids, &h->results);
     R.swept = true;
@@ -2829,22 +2843,18 @@ int gk_resident_audit(gk_engine* e, uint32_t k, uint32_t flags, gk_audit_out** o
     for (auto& c : R.chunks) {
       gk_table* t = c.table;
       const gk_eval_out* ev = c.ev;
-      for (uint32_t w = 0; w < ev->n_tiles; w++) beyond += (uint64_t)__builtin_popcountll(ev->too_big[w] & c.shown[w]);
+      beyond += shown_beyond(c);
       table_key_order(t);
       const uint32_t kc = std::min(k, t->n_reviews), cap = kc + 64;
       std::vector<uint32_t> pairs, idx, cnt, ovf;
       {
         std::shared_lock<std::shared_mutex> l(e->plan_rw);
         if (e->plan_dirty || c.plan_gen != e->plan_gen) return fail(GK_ERR_DEVICE, "the policies changed while gk_resident_audit ran: call it again");
-        dev_audit_select(t->dev, (uint32_t)e->plan_ids.size(), t->n_reviews, t->order, t->grp, c.shown, c.shown_gen, kc, cap, &pairs, &idx, &cnt, &ovf);
-        for (size_t gi = 0; gi < e->extra.size() && gi < t->views.size(); gi++) {   // further plan groups: rows appended
+        each_group(e, t, [&](const GroupAt& g) {   // the groups' rows, appended
           std::vector<uint32_t> p, r, n, o;
-          dev_audit_select(t->views[gi], (uint32_t)e->extra[gi]->ids.size(), t->n_reviews, t->order, t->grp, c.shown, c.shown_gen, kc, cap, &p, &r, &n, &o);
-          pairs.insert(pairs.end(), p.begin(), p.end());
-          idx.insert(idx.end(), r.begin(), r.end());
-          cnt.insert(cnt.end(), n.begin(), n.end());
-          ovf.insert(ovf.end(), o.begin(), o.end());
-        }
+          dev_audit_select(g.side.dev, g.nc, t->n_reviews, t->order, t->grp, c.shown, c.shown_gen, kc, cap, &p, &r, &n, &o);
+          append(pairs, std::move(p)); append(idx, std::move(r)); append(cnt, std::move(n)); append(ovf, std::move(o));
+        });
       }
       const uint32_t rows = std::min<uint32_t>((uint32_t)pairs.size(), nc);
       for (uint32_t row = 0; row < rows; row++) {
@@ -2912,11 +2922,7 @@ int gk_resident_audit(gk_engine* e, uint32_t k, uint32_t flags, gk_audit_out** o
       h->counts[row] = (uint32_t)cands[row].size();
       for (size_t i = 0; i < cands[row].size(); i++) {
         auto ins = path_of.emplace(cands[row][i].obj, (uint32_t)h->path_text.size());
-        if (ins.second) {
-          std::string js = "[";
-          for (const std::string& seg : R.objs[cands[row][i].obj].path) { if (js.size() > 1) js += ","; json_escape(seg, js); }
-          h->path_text.push_back(js + "]");
-        }
+        if (ins.second) { h->path_text.emplace_back(); append_path_json(R.objs[cands[row][i].obj].path, h->path_text.back()); }
         h->objects[(size_t)row * stride + i] = ins.first->second;
       }
     }
@@ -2960,11 +2966,8 @@ struct VerifyHolder {
 // table of a call fixes the constraint ids of the rows; a later one that sees other ids fails (the policies changed in between).
 static int verify_table(gk_engine* e, gk_table* t, uint32_t flags, uint32_t max_entries, const std::vector<uint64_t>* mask, uint32_t review_base, bool first, VerifyHolder* h) {
   ensure_plan(e);
-  if (t->dict_gen != e->dict_reg.gen())
-    return fail(GK_ERR_INVALID, "the table was flattened before a constraint with dictionary predicates was added (its <leaf>.$d rows are missing): create it again");
-  if (t->pruned && t->reads_gen != e->dict_reg.reads_gen())
-    return fail(GK_ERR_INVALID, "the pruned table was flattened before a constraint that reads other key paths was added (GK_TABLE_PRUNED): create it again");
-  if (!t->shard.shard_reviews.empty())
+  if (const char* why = table_stale(e, t)) return fail(GK_ERR_INVALID, why);
+  if (!t->sides[0].shard.shard_reviews.empty())
     return fail(GK_ERR_INVALID, "gk_table_verify: the table is set up as a shard (gk_table_sweep_sharded), its bitmaps live in the exchange buffer: verify a table of its own");
   const bool want_match = (flags & GK_VERIFY_WANT_MATCH) != 0;
   std::vector<size_t> differing;   // plan groups
@@ -2973,55 +2976,53 @@ static int verify_table(gk_engine* e, gk_table* t, uint32_t flags, uint32_t max_
     { std::lock_guard<std::mutex> gate(e->plan_gate); }   // (a plan change that is waiting goes first)
     std::shared_lock<std::shared_mutex> l(e->plan_rw);
     gen = e->plan_gen;
-    std::vector<uint32_t> ids = e->plan_ids;
-    for (auto& g : e->extra) ids.insert(ids.end(), g->ids.begin(), g->ids.end());
+    const std::vector<uint32_t> ids = all_ids(e);
     if (first) { h->ids = ids; h->m.begin((uint32_t)ids.size(), want_match); }
     else if (ids != h->ids) return fail(GK_ERR_DEVICE, "the policies changed while the verification ran: call it again");
-    const size_t ng = 1 + e->extra.size();
-    std::vector<DevPlan*> dp(ng, nullptr);
-    std::vector<const HostPlan*> hp(ng, nullptr);
-    { std::lock_guard<std::mutex> vl(e->variants_mu); for (size_t g = 0; g < ng; g++) dp[g] = plan_for_group(e, t, g, &hp[g]); }
-    while (t->views.size() < e->extra.size()) t->views.push_back(dev_table_view(t->dev));
-    while (t->vviews.size() < ng) t->vviews.push_back(dev_table_view(t->dev));
-    // the plans of the bytecode side: the plans themselves under EvalOptions::bytecode, or the backend's twins of them (kept per plan generation)
-    if (t->vtwins_gen != gen) { for (DevPlan* p : t->vtwins) dev_plan_free(p); t->vtwins.clear(); t->vtwins_gen = gen; }
-    while (t->vtwins.size() < ng) { const size_t g = t->vtwins.size(); t->vtwins.push_back(dev_verify_twin(e->opts.device, *hp[g], g == 0 ? e->big : e->extra[g - 1]->big)); }
-    auto plan_b = [&](size_t g) { return t->vtwins[g] ? t->vtwins[g] : dp[g]; };
-    auto side_a = [&](size_t g) { return g == 0 ? t->dev : t->views[g - 1]; };
+    const size_t ng = e->groups.size();
+    table_plans(e, t);
+    // the bytecode side of every group: a view of the table, and the plan it evaluates -- the group's own plan under EvalOptions::bytecode,
+    // or the backend's twin of it (kept while the plan generation stands)
+    each_group(e, t, [&](const GroupAt& g) {
+      gk_table::Side& s = g.side;
+      if (!s.vview) s.vview = dev_table_view(t->dev);
+      if (s.vtwin_gen != gen) { dev_plan_free(s.vtwin); s.vtwin = dev_verify_twin(e->opts.device, *s.host, g.grp.big); s.vtwin_gen = gen; }
+    });
     EvalOptions oa;
     oa.download = false;
     oa.want_match = want_match;
     oa.jit_wait = true;   // whatever the table's size: the bytecode kernel is not compared with itself
     EvalOptions ob = oa;
     ob.bytecode = true;
-    if (ng > 1) for (size_t g = 0; g < ng; g++) dev_jit_prefetch(dp[g], side_a(g));   // (the builds compile side by side)
+    if (ng > 1) each_group(e, t, [&](const GroupAt& g) { dev_jit_prefetch(g.side.plan, g.side.dev); });   // (the builds compile side by side)
     std::vector<EvalOut> A(ng), B(ng);
-    for (size_t g = 0; g < ng; g++) dev_verify_eval(dp[g], side_a(g), oa, &A[g]);
-    for (size_t g = 0; g < ng; g++) dev_verify_eval(plan_b(g), t->vviews[g], ob, &B[g]);
+    each_group(e, t, [&](const GroupAt& g) { dev_verify_eval(g.side.plan, g.side.dev, oa, &A[g.g]); });
+    each_group(e, t, [&](const GroupAt& g) { dev_verify_eval(g.side.vtwin ? g.side.vtwin : g.side.plan, g.side.vview, ob, &B[g.g]); });
     t->last_nc = (uint32_t)ids.size(); t->last_ids = ids;   // (the table's bitmaps are this evaluation's now, as after gk_table_eval)
     // fault injection (gk_debug_set "verify_flip"): one bit or word of the bytecode side
     const int64_t flip = g_debug_verify_flip.load();
     const uint32_t f_kind = (uint32_t)((uint64_t)flip >> 56) & 0x7Fu, f_row = (uint32_t)((uint64_t)flip >> 32) & 0x7FFFFFu, f_review = (uint32_t)((uint64_t)flip & 0xFFFFFFFFu);
     const bool f_word = (((uint64_t)flip >> 55) & 1u) != 0, f_here = flip >= 0 && f_review >= review_base && f_review - review_base < t->n_reviews;
     uint32_t row_base = 0;
-    for (size_t g = 0; g < ng; g++) {
-      const uint32_t nc = A[g].n_constraints;
+    each_group(e, t, [&](const GroupAt& g) {
+      const EvalOut& a = A[g.g];
+      const uint32_t nc = a.n_constraints;
       h->n_plan_groups++;
-      h->a_ms += A[g].kernel_ms; h->b_ms += B[g].kernel_ms;
-      h->hash = h->n_plan_groups == 1 ? A[g].kernel_hash : h->hash * 1099511628211ull ^ A[g].kernel_hash;   // (as gk_eval_out: one figure that names all the texts)
-      if (f_here && nc && t->n_reviews && (f_kind == VERIFY_TOO_BIG ? g == 0 : f_row >= row_base && f_row - row_base < nc))
-        dev_verify_flip(t->vviews[g], nc, f_kind, f_kind == VERIFY_TOO_BIG ? 0 : f_row - row_base, f_review - review_base, f_word);
+      h->a_ms += a.kernel_ms; h->b_ms += B[g.g].kernel_ms;
+      h->hash = h->n_plan_groups == 1 ? a.kernel_hash : h->hash * 1099511628211ull ^ a.kernel_hash;   // (as gk_eval_out: one figure that names all the texts)
+      if (f_here && nc && t->n_reviews && (f_kind == VERIFY_TOO_BIG ? g.g == 0 : f_row >= row_base && f_row - row_base < nc))
+        dev_verify_flip(g.side.vview, nc, f_kind, f_kind == VERIFY_TOO_BIG ? 0 : f_row - row_base, f_review - review_base, f_word);
       // (else: no specialised build for this group -- GK_NO_JIT, a failed build, a quarantined group, whatever a backend that cannot take
       //  a plan off its specialised code goes on running for it: nothing to compare)
-      if (A[g].specialised && !e->quarantined.count(g)) {
+      if (a.specialised && !e->quarantined.count(g.g)) {
         h->specialised_groups++;
         VerifyDiff d;
-        dev_verify_diff(side_a(g), t->vviews[g], nc, t->n_reviews, want_match, mask, max_entries, &d);
+        dev_verify_diff(g.side.dev, g.side.vview, nc, t->n_reviews, want_match, mask, max_entries, &d);
         h->m.add(d, row_base, review_base);
-        if (d.entries_total != 0 && (flags & GK_VERIFY_QUARANTINE)) differing.push_back(g);
+        if (d.entries_total != 0 && (flags & GK_VERIFY_QUARANTINE)) differing.push_back(g.g);
       }
       row_base += nc;
-    }
+    });
     h->n_reviews += t->n_reviews;
   }
   if (!differing.empty()) {
@@ -3032,7 +3033,7 @@ static int verify_table(gk_engine* e, gk_table* t, uint32_t flags, uint32_t max_
       for (size_t g : differing) {
         // the plan that ran -- the table-sized variant of a resident table -- and every other plan of the group: same formulas, same generator
         e->quarantined.insert(g);
-        dev_plan_no_jit(g == 0 ? e->dev_plan : e->extra[g - 1]->dev);
+        dev_plan_no_jit(e->groups[g]->dev);
         for (auto& v : e->variants) if (v.first.first == g && v.second->dev) dev_plan_no_jit(v.second->dev);
         h->quarantined_groups++;
         fprintf(stderr, "[gkgpu] the plan-specialised kernel disagrees with the bytecode kernel (gk_table_verify), using the bytecode kernel for this plan\n");
@@ -3099,10 +3100,10 @@ int gk_resident_verify(gk_engine* e, uint32_t flags, uint32_t max_entries, gk_ve
     verify_publish(h.get(), flags, max_entries);
     for (const gk_verify_entry& en : h->entries) {
       size_t ci = std::upper_bound(base.begin(), base.end(), en.review) - base.begin();
-      std::string js = "[";
-      if (ci > 0 && en.review - base[ci - 1] < R.chunks[ci - 1].obj_of_slot.size())
-        for (const std::string& seg : R.objs[R.chunks[ci - 1].obj_of_slot[en.review - base[ci - 1]]].path) { if (js.size() > 1) js += ","; json_escape(seg, js); }
-      h->path_text.push_back(js + "]");
+      static const std::vector<std::string> no_path;
+      const bool known = ci > 0 && en.review - base[ci - 1] < R.chunks[ci - 1].obj_of_slot.size();
+      h->path_text.emplace_back();
+      append_path_json(known ? R.objs[R.chunks[ci - 1].obj_of_slot[en.review - base[ci - 1]]].path : no_path, h->path_text.back());
     }
     for (std::string& p : h->path_text) h->paths.push_back(&p[0]);
     if (entry_paths) *entry_paths = h->paths.empty() ? nullptr : h->paths.data();
@@ -3147,19 +3148,6 @@ struct ViolationsHolder {
 };
 const char* const k_stream_moved = "the resident set or the policies changed since the stream began: start again with cursor 0";
 
-// the plan groups of a chunk as the device sees them: (table or view, rows, first row among all constraints).  plan_rw held shared.
-struct ViolGroup { const DevTable* dev; uint32_t nc, row0; };
-std::vector<ViolGroup> viol_groups(gk_engine* e, gk_table* t) {
-  std::vector<ViolGroup> g;
-  uint32_t row0 = (uint32_t)e->plan_ids.size();
-  g.push_back(ViolGroup{t->dev, row0, 0});
-  for (size_t gi = 0; gi < e->extra.size() && gi < t->views.size(); gi++) {
-    g.push_back(ViolGroup{t->views[gi], (uint32_t)e->extra[gi]->ids.size(), row0});
-    row0 += (uint32_t)e->extra[gi]->ids.size();
-  }
-  return g;
-}
-
 // The index of one chunk: per plan group the device counts the shown reviews with a bit per bitmap word (dev_viol_index) and keeps the
 // prefix sum that places its entries.  Where nothing else can add an entry -- one group, no autoreject bit, no host-evaluated
 // violation: the common state -- those counts ARE the index and 4 bytes per word come back.  Otherwise an object may be named by
@@ -3168,32 +3156,31 @@ void resident_viol_index(gk_engine* e, gk_engine::ResChunk& c, const std::vector
   gk_table* t = c.table;
   const gk_eval_out* ev = c.ev;
   const uint32_t pw = (t->n_reviews + 63u) / 64u, nt = ev->n_tiles, rows = std::min<uint32_t>(ev->n_constraints, (uint32_t)ids.size());
-  std::vector<uint64_t> extra(pw, 0);
+  std::vector<uint64_t> host_words(pw, 0);
   for (uint32_t row = 0; row < rows; row++)
-    for (uint32_t w = 0; w < pw && w < nt; w++) extra[w] |= ev->err[(size_t)row * nt + w];
+    for (uint32_t w = 0; w < pw && w < nt; w++) host_words[w] |= ev->err[(size_t)row * nt + w];
   {
     std::lock_guard<std::mutex> hl(t->host_mu);
     if (t->host_ids == ids)
-      for (auto& hp : t->host_viol) if (hp.first < rows && hp.second < t->n_reviews) extra[hp.second / 64] |= 1ull << (hp.second % 64);
+      for (auto& hp : t->host_viol) if (hp.first < rows && hp.second < t->n_reviews) host_words[hp.second / 64] |= 1ull << (hp.second % 64);
   }
-  bool has_extra = false;
-  for (uint32_t w = 0; w < pw; w++) { extra[w] &= w < c.shown.size() ? c.shown[w] : 0ull; has_extra = has_extra || extra[w]; }
-  const std::vector<ViolGroup> groups = viol_groups(e, t);
-  const bool merged = has_extra || groups.size() > 1;
+  bool has_host = false;
+  for (uint32_t w = 0; w < pw; w++) { host_words[w] &= w < c.shown.size() ? c.shown[w] : 0ull; has_host = has_host || host_words[w]; }
+  const bool merged = has_host || (e->groups.size() > 1 && t->sides.size() > 1);
   std::vector<uint64_t> any(pw, 0), a;
   std::vector<uint32_t> cnt(pw, 0), n;
-  for (const ViolGroup& g : groups) {
-    if (g.nc == 0) continue;
-    dev_viol_index(g.dev, g.nc, t->n_reviews, c.shown, c.shown_gen, &n, merged ? &a : nullptr);
+  each_group(e, t, [&](const GroupAt& g) {
+    if (g.nc == 0) return;
+    dev_viol_index(g.side.dev, g.nc, t->n_reviews, c.shown, c.shown_gen, &n, merged ? &a : nullptr);
     if (n.size() != pw || (merged && a.size() != pw)) throw std::runtime_error("dev_viol_index: wrong size");
     if (merged) for (uint32_t w = 0; w < pw; w++) any[w] |= a[w];
     else cnt = n;
-  }
+  });
   c.vs_prefix.assign((size_t)pw + 1, 0);
-  for (uint32_t w = 0; w < pw; w++) c.vs_prefix[w + 1] = c.vs_prefix[w] + (merged ? (uint64_t)__builtin_popcountll(any[w] | extra[w]) : cnt[w]);
-  c.vs_extra.clear();
+  for (uint32_t w = 0; w < pw; w++) c.vs_prefix[w + 1] = c.vs_prefix[w] + (merged ? (uint64_t)__builtin_popcountll(any[w] | host_words[w]) : cnt[w]);
+  c.vs_host_slots.clear();
   for (uint32_t w = 0; w < pw; w++)
-    for (uint64_t m = extra[w]; m; m &= m - 1) c.vs_extra.push_back(w * 64u + (uint32_t)__builtin_ctzll(m));
+    for (uint64_t m = host_words[w]; m; m &= m - 1) c.vs_host_slots.push_back(w * 64u + (uint32_t)__builtin_ctzll(m));
   c.vs_plan_gen = c.plan_gen; c.vs_shown_gen = c.shown_gen;
 }
 }  // namespace
@@ -3243,8 +3230,7 @@ int gk_resident_violations(gk_engine* e, uint64_t cursor, uint32_t max_objects, 
       for (auto& c : R.chunks) {
         chunk_words.push_back((uint32_t)(c.vs_prefix.size() - 1));
         total += c.vs_prefix.back();
-        const gk_eval_out* ev = c.ev;
-        for (uint32_t w = 0; w < ev->n_tiles && w < c.shown.size(); w++) beyond += (uint64_t)__builtin_popcountll(ev->too_big[w] & c.shown[w]);
+        beyond += shown_beyond(c);
       }
       // where the page begins: the cursor's word, or the first word of the set that has entries
       ViolCursor at;
@@ -3268,24 +3254,24 @@ int gk_resident_violations(gk_engine* e, uint64_t cursor, uint32_t max_objects, 
         const uint32_t nt = ev->n_tiles, rows = std::min<uint32_t>(ev->n_constraints, nc);
         page_chunk = at.chunk;
         // the device's entries of every plan group, then the slots only the host knows
-        const std::vector<ViolGroup> groups = viol_groups(e, t);
-        std::vector<std::vector<uint32_t>> rev(groups.size());
-        std::vector<std::vector<uint64_t>> msk(groups.size());
-        for (size_t gi = 0; gi < groups.size(); gi++) {
-          if (groups[gi].nc == 0) continue;
-          dev_viol_entries(groups[gi].dev, groups[gi].nc, t->n_reviews, c.shown, c.shown_gen, w0, w1, &rev[gi], &msk[gi]);
-          slots = slots.empty() ? rev[gi] : viol_merge_slots(slots, rev[gi]);
-        }
-        const auto x0 = std::lower_bound(c.vs_extra.begin(), c.vs_extra.end(), w0 * 64u);
-        const auto x1 = std::lower_bound(x0, c.vs_extra.end(), (uint64_t)w1 * 64u, [](uint32_t s, uint64_t lim) { return s < lim; });
-        const std::vector<uint32_t> extra(x0, x1);
-        if (!extra.empty()) slots = viol_merge_slots(slots, extra);
+        std::vector<std::vector<uint32_t>> rev(e->groups.size());
+        std::vector<std::vector<uint64_t>> msk(e->groups.size());
+        each_group(e, t, [&](const GroupAt& g) {
+          if (g.nc == 0) return;
+          dev_viol_entries(g.side.dev, g.nc, t->n_reviews, c.shown, c.shown_gen, w0, w1, &rev[g.g], &msk[g.g]);
+          slots = slots.empty() ? rev[g.g] : viol_merge_slots(slots, rev[g.g]);
+        });
+        const auto x0 = std::lower_bound(c.vs_host_slots.begin(), c.vs_host_slots.end(), w0 * 64u);
+        const auto x1 = std::lower_bound(x0, c.vs_host_slots.end(), (uint64_t)w1 * 64u, [](uint32_t s, uint64_t lim) { return s < lim; });
+        const std::vector<uint32_t> host_slots(x0, x1);
+        if (!host_slots.empty()) slots = viol_merge_slots(slots, host_slots);
         if (slots.size() != c.vs_prefix[w1] - c.vs_prefix[w0]) throw std::runtime_error("gk_resident_violations: the page's entries do not add up to the chunk's index");
         h->viol.assign(slots.size() * (size_t)mw, 0); h->err.assign(slots.size() * (size_t)mw, 0);
-        for (size_t gi = 0; gi < groups.size(); gi++)
-          if (groups[gi].nc && !viol_scatter(slots, mw, rev[gi], msk[gi], groups[gi].nc, groups[gi].row0, &h->viol))
+        each_group(e, t, [&](const GroupAt& g) {
+          if (g.nc && !viol_scatter(slots, mw, rev[g.g], msk[g.g], g.nc, g.row0, &h->viol))
             throw std::runtime_error("gk_resident_violations: a plan group's entries do not fit the page");
-        for (uint32_t slot : extra) {   // autoreject pairs: the downloaded error bitmap
+        });
+        for (uint32_t slot : host_slots) {   // autoreject pairs: the downloaded error bitmap
           const size_t i = viol_find(slots, slot);
           for (uint32_t row = 0; row < rows; row++)
             if ((ev->err[(size_t)row * nt + slot / 64] >> (slot % 64)) & 1ull) h->err[i * mw + row / 64] |= 1ull << (row % 64);
@@ -3324,10 +3310,7 @@ int gk_resident_violations(gk_engine* e, uint64_t cursor, uint32_t max_objects, 
       at.reserve(slots.size());
       for (uint32_t slot : slots) {
         at.push_back(a.size());
-        a += '[';
-        bool first = true;
-        for (const std::string& seg : R.objs[pc->obj_of_slot[slot]].path) { if (!first) a += ','; first = false; json_escape(seg, a); }
-        a += ']';
+        append_path_json(R.objs[pc->obj_of_slot[slot]].path, a);
         a += '\0';
       }
       h->paths.reserve(slots.size());
@@ -3641,7 +3624,7 @@ int gk_table_review_words(gk_engine* e, const gk_table* t, char** text_out) {
   try {
     ensure_plan(e);
     std::shared_lock<std::shared_mutex> l(e->plan_rw);
-    const HostPlan& p = e->fast;
+    const HostPlan& p = e->groups[0]->fast;
     const HostTable& h = t->host;
     const uint32_t n_groups = h.n_tiles(), S = h.n_slots();
     if (h.tile_idx.size() != (size_t)n_groups * (S + 1u)) return fail(GK_ERR_INVALID, "the table did not keep its slot index: gk_debug_set(\"keep_slot_index\", 1) before it is created");
@@ -3695,7 +3678,7 @@ int gk_dump(gk_engine* e, char** text_out) {
     ensure_plan(e);
     std::ostringstream os;
     std::shared_lock<std::shared_mutex> l(e->plan_rw);
-    const HostPlan& p = e->fast;
+    const HostPlan& p = e->groups[0]->fast;
     os << "constraints=" << p.dims.n_constraints << " viol_formulas=" << p.n_viol << " match_formulas=" << p.n_match
        << " preds=" << p.dims.n_preds << " scopes=" << p.dims.n_scopes << " code_words=" << p.dims.n_code
        << " gwords=" << p.dims.n_gwords << " acc_words=" << p.dims.acc_words << " lds_bytes_per_64_reviews=" << p.dims.acc_words * 256
