@@ -95,6 +95,22 @@ void dev_viol_index(const DevTable* t, uint32_t nc, uint32_t n_reviews, const st
                     std::vector<uint32_t>* cnt, std::vector<uint64_t>* any = nullptr);
 void dev_viol_entries(const DevTable* t, uint32_t nc, uint32_t n_reviews, const std::vector<uint64_t>& shown, uint64_t shown_gen, uint32_t w0, uint32_t w1,
                       std::vector<uint32_t>* reviews, std::vector<uint64_t>* masks);
+// table violation stream (gk_table_violations): every review with a bit in at least one row of the violation OR the autoreject bitmap of
+// the most recent evaluation, over ALL plan groups at once.  A side is what one group evaluated into (the table or a view of it), its
+// rows and its first row among all constraints; sides without rows are skipped.  Reviews with a too_big bit in any side are masked
+// (their device bits are unspecified) and counted in *beyond.  dev_tviol_index: cnt[w] = entries of bitmap word w ([ceil(n_reviews /
+// 64)]; `any`, when asked for, the reviews themselves).  dev_tviol_entries: the entries of the words [w0, w1), reviews ascending, masks
+// [entries][ceil(total rows / 64)] with bit row0 + r = row r of the side; `off` = the exclusive prefix sum of cnt ([words + 1], the
+// caller keeps it) places them, and the call throws when it does not fit the bitmaps.  Both throw while launches of a side are still to
+// be collected.  *ms: HIP-event time of the call's kernels (the CPU stand-in: 0).
+struct TviolSide { const DevTable* t = nullptr; uint32_t nc = 0, row0 = 0; };
+void dev_tviol_index(const std::vector<TviolSide>& sides, uint32_t n_reviews, std::vector<uint32_t>* cnt, std::vector<uint64_t>* any, uint64_t* beyond, float* ms);
+void dev_tviol_entries(const std::vector<TviolSide>& sides, uint32_t n_reviews, const std::vector<uint32_t>& off, uint32_t w0, uint32_t w1,
+                       std::vector<uint32_t>* reviews, std::vector<uint64_t>* viol, std::vector<uint64_t>* err, float* ms);
+// what a collected evaluation of `t` answered, for a backend that cannot read its result buffers back later (the CPU stand-in keeps the
+// three bitmaps beside the table's address; the device reads its own buffers and does nothing here) / the table (view) is going away
+void dev_tviol_note(const DevTable* t, const EvalOut& o);
+void dev_tviol_forget(const DevTable* t);
 // the violation bitmap [nc][n_tiles] of the table's most recent evaluation (device -> host copy)
 void dev_last_viol(const DevTable* t, uint32_t nc, std::vector<uint64_t>* viol);
 // ---- the plan-specialised kernel checked against the bytecode kernel (gk_table_verify).

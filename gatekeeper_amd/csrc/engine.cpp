@@ -32,6 +32,7 @@
 #include "regex.hpp"
 #include "review_words.hpp"
 #include "verify_merge.hpp"
+#include "table_stream.hpp"
 #include "viol_stream.hpp"
 
 using namespace gk;
@@ -452,6 +453,17 @@ struct gk_table {
   std::vector<std::pair<uint32_t, uint32_t>> host_viol, host_err;
   std::vector<uint32_t> host_ids;
   std::mutex host_mu;
+  // gk_table_violations.  ts_gen, the stream generation, moves with every launch that writes the table's result buffers (table_results_move:
+  // evaluation, verification, a sharded sweep): a cursor carries it.  The host evaluation stamps what it publishes -- host_done, the
+  // reviews it answered, beside host_viol / host_err -- with the generation of ITS evaluation (host_gen): the stream of a later
+  // evaluation that did not complete on the host (GK_EVAL_NO_DOWNLOAD) reads none of them.  eval_plan_gen: the plan generation the
+  // bitmaps belong to (0: never collected); ts_pending: GK_EVAL_ASYNC launches wait to be collected.  The index is kept while ts_gen
+  // stands (ts_index_gen): ts_prefix over all entries (table_stream.hpp), ts_dev_off over the device's alone (places its entries).
+  uint32_t ts_gen = 0, host_gen = 0, ts_index_gen = 0;
+  uint64_t eval_plan_gen = 0, ts_beyond = 0;
+  bool ts_pending = false;
+  std::vector<uint32_t> host_done, ts_dev_off;
+  std::vector<uint64_t> ts_prefix;
   uint32_t n_reviews = 0;
   uint32_t rpt = GK_RPT_MIN;                // reviews per row group of this table
   uint64_t dict_gen = 0;                    // generation of the dictionary-predicate registry the rows were flattened under
@@ -508,6 +520,10 @@ std::vector<uint32_t> all_ids(const gk_engine* e) {
 void table_sides(const gk_engine* e, gk_table* t) {
   while (t->sides.size() < e->groups.size()) { gk_table::Side s; s.dev = dev_table_view(t->dev); t->sides.push_back(s); }
 }
+
+// a launch is about to write the table's result buffers (or a collecting call to finish them): gk_table_violations' stream generation
+// moves, so that no cursor handed out before is answered from the new bitmaps
+void table_results_move(gk_table* t) { t->ts_gen = viol_next_gen(t->ts_gen); }
 
 // One plan group as seen from one table: the engine's group `grp` (its base plan: grp.dev), the table's side of it (what it evaluates
 // into: side.dev; the plan this table runs it on, once table_plans chose it: side.plan), its number of bitmap rows and its first row
@@ -1715,6 +1731,7 @@ void gk_table_free(gk_table* t) {
     if (s.vview) { dev_verify_forget(s.vview); dev_table_free(s.vview); }
     dev_plan_free(s.vtwin);
     dev_verify_forget(s.dev);
+    dev_tviol_forget(s.dev);
     dev_table_free(s.dev);
   }
   delete t;
@@ -1749,6 +1766,7 @@ int gk_table_eval(gk_engine* e, gk_table* t, uint32_t flags, gk_eval_out** out) 
       { std::lock_guard<std::mutex> gate(e->plan_gate); }   // (a plan change that is waiting goes first)
       std::shared_lock<std::shared_mutex> l(e->plan_rw);
       h->ids = all_ids(e);
+      table_results_move(t);
       if (flags & GK_EVAL_WANT_LIST) opt.list_capacity = std::max<uint32_t>(1024, t->n_reviews * 4u);
       table_plans(e, t);   // every plan group: its side of the table, its table-sized variant
       // every plan group is LAUNCHED before any is collected: the groups work on their own streams (sides of the table) and
@@ -1759,15 +1777,17 @@ int gk_table_eval(gk_engine* e, gk_table* t, uint32_t flags, gk_eval_out** out) 
         each_group(e, t, [&](const GroupAt& g) { dev_eval_launch(g.side.plan, g.side.dev, opt); });
       }
       if (flags & GK_EVAL_ASYNC) {   // enqueue only; a later call without GK_EVAL_ASYNC collects
+        t->ts_pending = true;
         *out = nullptr;
         return GK_OK;
       }
       // collected in group order: the primary group's answer is the call's, the rows of every further group are appended below it
       each_group(e, t, [&](const GroupAt& g) {
         EvalOut& o = h->out;
-        if (g.g == 0) { dev_eval_finish(g.side.plan, g.side.dev, opt, &o); h->lds_bytes = o.lds_bytes; return; }
+        if (g.g == 0) { dev_eval_finish(g.side.plan, g.side.dev, opt, &o); dev_tviol_note(g.side.dev, o); h->lds_bytes = o.lds_bytes; return; }
         EvalOut og;
         dev_eval_finish(g.side.plan, g.side.dev, opt, &og);
+        dev_tviol_note(g.side.dev, og);
         const uint32_t row_base = o.n_constraints;
         o.viol.insert(o.viol.end(), og.viol.begin(), og.viol.end());
         o.err.insert(o.err.end(), og.err.begin(), og.err.end());
@@ -1784,6 +1804,8 @@ int gk_table_eval(gk_engine* e, gk_table* t, uint32_t flags, gk_eval_out** out) 
         o.n_constraints += og.n_constraints;
         o.d_viol = o.d_err = o.d_counts = nullptr;   // not one contiguous device buffer any more
       });
+      t->ts_pending = false;
+      t->eval_plan_gen = e->plan_gen;   // (what gk_table_violations streams: these bitmaps, of this plan generation)
     }
     // reviews the device could not evaluate (too_big) are answered by the engine's own exact evaluator where their text is at hand
     if (opt.download && !(flags & GK_EVAL_DEVICE_ONLY)) complete_on_host(e, t, h.get(), opt.want_match, (flags & GK_EVAL_WANT_LIST) != 0);
@@ -1973,7 +1995,11 @@ static void complete_on_host(gk_engine* e, gk_table* t, EvalHolder* h, bool want
   std::vector<std::pair<uint32_t, uint32_t>> add_viol, add_err;
   struct Publish {
     gk_table* t; EvalHolder* h; std::vector<std::pair<uint32_t, uint32_t>>*v, *er;
-    ~Publish() { std::lock_guard<std::mutex> hl(t->host_mu); t->host_viol.swap(*v); t->host_err.swap(*er); t->host_ids = h->ids; }
+    ~Publish() {
+      std::lock_guard<std::mutex> hl(t->host_mu);
+      t->host_viol.swap(*v); t->host_err.swap(*er); t->host_ids = h->ids;
+      t->host_done = h->host_evaluated; t->host_gen = t->ts_gen;   // (gk_table_violations: the pairs of THIS evaluation)
+    }
   } publish{t, h, &add_viol, &add_err};
   if (env_off || tl_host_completion_depth > 0) return;
   struct Depth { Depth() { tl_host_completion_depth++; } ~Depth() { tl_host_completion_depth--; } } depth_guard;
@@ -2499,6 +2525,7 @@ int gk_table_sweep_sharded(gk_engine* e, gk_table* t, uint32_t flags, gk_shard_o
     auto plan_of = [](const GroupAt& g) { const DevPlan* p = g.grp.dev; if (g.g == 0) p = g.side.plan; return p; };
     const size_t n_groups = e->groups.size();
     const ShardInfo& shard0 = t->sides[0].shard;
+    table_results_move(t);
     if (t->shard_gen != e->plan_gen || shard0.shard_reviews.empty()) {   // (collective) once per table and plan
       each_group(e, t, [&](const GroupAt& g) { dev_shard_setup(g.side.dev, e->comm, g.nc, &g.side.shard); });
       t->shard_gen = e->plan_gen;
@@ -2996,9 +3023,11 @@ static int verify_table(gk_engine* e, gk_table* t, uint32_t flags, uint32_t max_
     ob.bytecode = true;
     if (ng > 1) each_group(e, t, [&](const GroupAt& g) { dev_jit_prefetch(g.side.plan, g.side.dev); });   // (the builds compile side by side)
     std::vector<EvalOut> A(ng), B(ng);
-    each_group(e, t, [&](const GroupAt& g) { dev_verify_eval(g.side.plan, g.side.dev, oa, &A[g.g]); });
+    table_results_move(t);
+    each_group(e, t, [&](const GroupAt& g) { dev_verify_eval(g.side.plan, g.side.dev, oa, &A[g.g]); dev_tviol_note(g.side.dev, A[g.g]); });
     each_group(e, t, [&](const GroupAt& g) { dev_verify_eval(g.side.vtwin ? g.side.vtwin : g.side.plan, g.side.vview, ob, &B[g.g]); });
     t->last_nc = (uint32_t)ids.size(); t->last_ids = ids;   // (the table's bitmaps are this evaluation's now, as after gk_table_eval)
+    t->ts_pending = false; t->eval_plan_gen = gen;
     // fault injection (gk_debug_set "verify_flip"): one bit or word of the bytecode side
     const int64_t flip = g_debug_verify_flip.load();
     const uint32_t f_kind = (uint32_t)((uint64_t)flip >> 56) & 0x7Fu, f_row = (uint32_t)((uint64_t)flip >> 32) & 0x7FFFFFu, f_review = (uint32_t)((uint64_t)flip & 0xFFFFFFFFu);
@@ -3361,6 +3390,169 @@ int gk_resident_violations(gk_engine* e, uint64_t cursor, uint32_t max_objects, 
 }
 
 void gk_violations_free(gk_violations_out* o) { if (o) delete reinterpret_cast<ViolationsHolder*>(o); }
+
+// ---- gk_table_violations: every review of a table with at least one result in its most recent evaluation, in pages (table_stream.hpp
+// holds the pure part; the device compacts both bitmaps of all plan groups: dev_tviol_index / dev_tviol_entries)
+namespace {
+struct TableViolationsHolder {
+  gk_table_violations_out pub;   // first member
+  std::vector<uint32_t> ids, reviews;
+  std::vector<uint64_t> viol, err;
+  std::vector<std::string> result_text;
+  std::vector<const char*> results;
+};
+const char* const k_table_stream_moved = "the table was evaluated again or the policies changed since the stream began: start again with cursor 0";
+
+// the rows of one entry as gk_query's JSON: ascending bitmap row; an err bit gives gk_render_error's row, a viol bit gk_render's rows
+std::string table_entry_json(gk_engine* e, gk_table* t, const std::vector<uint32_t>& ids, uint32_t r, const uint64_t* viol, const uint64_t* err) {
+  ReviewDoc tmp;
+  const ReviewDoc* doc = doc_for(e, t, r, &tmp);
+  if (!doc) throw std::runtime_error("review document unavailable");
+  std::string out = "[";
+  std::shared_lock<std::shared_mutex> l(e->mu);
+  for (uint32_t row = 0; row < ids.size(); row++) {
+    const bool is_err = (err[row / 64] >> (row % 64)) & 1ull, is_viol = (viol[row / 64] >> (row % 64)) & 1ull;
+    if (!is_err && !is_viol) continue;
+    const uint32_t cid = ids[row];
+    if (cid >= e->constraints.size()) throw std::runtime_error("unknown constraint id");
+    const ConstraintRec& c = e->constraints[cid];
+    if (is_err) {
+      ValuePairs o{{Value::string("constraint"), Value::integer(cid)}, {Value::string("msg"), Value::string(autoreject_message(c.match, *doc))},
+                   {Value::string("autoreject"), Value::boolean(true)}, {Value::string("details"), Value::object({})}};
+      if (out.size() > 1) out += ",";
+      out += to_json(Value::object(o));
+    }
+    if (!is_viol) continue;
+    auto it = e->templates.find(lower_str(c.kind));
+    // (as gk_query: a flagged pair that renders nothing is a disagreement between the plan and the evaluator, never "no results")
+    if (it == e->templates.end()) throw std::runtime_error("device / renderer disagree: constraint " + c.kind + "/" + c.name + " has no template");
+    const auto vs = it->second->render(doc->request, c.params, e->inventory);
+    if (vs.empty()) throw std::runtime_error("device / renderer disagree: the plan reports a violation of " + c.kind + "/" + c.name + " that the evaluator does not render");
+    for (auto& v : vs) {
+      static const Value k_constraint = Value::string("constraint"), k_msg = Value::string("msg"), k_details = Value::string("details"), no_details = Value::object({});
+      ValuePairs o{{k_constraint, Value::integer(cid)}, {k_details, v.details.defined() ? v.details : no_details}, {k_msg, Value::string(v.msg)}};
+      if (out.size() > 1) out += ",";
+      out += to_json(Value::object(o));
+    }
+  }
+  return out + "]";
+}
+}  // namespace
+
+int gk_table_violations(gk_engine* e, gk_table* t, uint64_t cursor, uint32_t max_entries, uint32_t flags, gk_table_violations_out** out) {
+  if (!e || !t || !out) return fail(GK_ERR_INVALID, "NULL argument");
+  if ((flags & GK_VIOLATIONS_RENDER) && t->docs.size() != t->n_reviews && t->texts.size() != t->n_reviews)
+    return fail(GK_ERR_INVALID, "gk_table_violations: GK_VIOLATIONS_RENDER needs a table created with GK_TABLE_KEEP_DOCS / GK_TABLE_KEEP_TEXT");
+  try {
+    if (const char* why = table_stale(e, t)) return fail(GK_ERR_INVALID, cursor ? k_table_stream_moved : why);   // (stale: the policies changed)
+    std::unique_ptr<TableViolationsHolder> h(new TableViolationsHolder());
+    const uint32_t pw = (t->n_reviews + 63u) / 64u;
+    float device_ms = 0;
+    uint64_t next_cursor = 0, beyond = 0;
+    {
+      std::shared_lock<std::shared_mutex> l(e->plan_rw);
+      if (!t->sides.empty() && !t->sides[0].shard.shard_reviews.empty())
+        return fail(GK_ERR_INVALID, "gk_table_violations: the table is set up as a shard (gk_table_sweep_sharded), its bitmaps live in the exchange buffer: stream a table of its own");
+      if (t->ts_pending) return fail(GK_ERR_INVALID, "gk_table_violations: launches of the table are still to be collected (gk_table_eval without GK_EVAL_ASYNC)");
+      if (t->ts_gen == 0 || t->eval_plan_gen == 0) return fail(GK_ERR_INVALID, "gk_table_violations: evaluate the table first (gk_table_eval)");
+      if (e->plan_dirty || e->plan_gen != t->eval_plan_gen)
+        return fail(GK_ERR_INVALID, cursor ? k_table_stream_moved : "gk_table_violations: the policies changed since the table was evaluated: evaluate it again (gk_table_eval)");
+      h->ids = t->last_ids;
+      const uint32_t nc = (uint32_t)h->ids.size(), mw = (nc + 63u) / 64u;
+      std::vector<TviolSide> sides;
+      uint32_t rows = 0;
+      each_group(e, t, [&](const GroupAt& g) { sides.push_back(TviolSide{g.side.dev, g.nc, g.row0}); rows = g.row0 + g.nc; });
+      if (rows != nc) return fail(GK_ERR_INVALID, "gk_table_violations: evaluate the table first (gk_table_eval)");
+      // what the host evaluation of THIS evaluation added (another evaluation's, another policy set's: none of it)
+      TablePairs hv, he;
+      size_t n_done = 0;
+      {
+        std::lock_guard<std::mutex> hl(t->host_mu);
+        if (t->host_gen == t->ts_gen && t->host_ids == h->ids) { hv = t->host_viol; he = t->host_err; n_done = t->host_done.size(); }
+      }
+      uint32_t w0 = 0;
+      if (cursor == 0) {
+        if (t->ts_index_gen != t->ts_gen || t->ts_prefix.size() != (size_t)pw + 1) {   // the index, once per evaluation
+          std::vector<uint64_t> host_words;
+          if (!hv.empty() || !he.empty()) host_words = table_host_words(hv, he, nc, t->n_reviews);
+          std::vector<uint32_t> cnt;
+          std::vector<uint64_t> any;
+          uint64_t dev_beyond = 0;
+          dev_tviol_index(sides, t->n_reviews, &cnt, host_words.empty() ? nullptr : &any, &dev_beyond, &device_ms);
+          if (cnt.size() != pw || !table_prefix(cnt, any, host_words, &t->ts_prefix)) throw std::runtime_error("dev_tviol_index: wrong size");
+          t->ts_dev_off.assign((size_t)pw + 1, 0);
+          for (uint32_t w = 0; w < pw; w++) t->ts_dev_off[w + 1] = t->ts_dev_off[w] + cnt[w];
+          t->ts_beyond = dev_beyond > n_done ? dev_beyond - n_done : 0;   // (every host-answered review had its too_big bit set)
+          t->ts_index_gen = t->ts_gen;
+        }
+        w0 = viol_next_word(t->ts_prefix, 0);
+      } else {
+        if (t->ts_index_gen != t->ts_gen || t->ts_prefix.size() != (size_t)pw + 1 || !table_cursor_check(cursor, t->ts_gen, pw, &w0)) return fail(GK_ERR_INVALID, k_table_stream_moved);
+        if (viol_next_word(t->ts_prefix, w0) != w0) return fail(GK_ERR_INVALID, k_table_stream_moved);   // (no page begins at a word without entries)
+      }
+      beyond = t->ts_beyond;
+      h->pub.total_entries = t->ts_prefix.back();
+      if (w0 < pw) {
+        const uint32_t w1 = viol_page_end(t->ts_prefix, w0, max_entries);
+        std::vector<uint32_t> rev;
+        std::vector<uint64_t> dv, de;
+        float ms = 0;
+        dev_tviol_entries(sides, t->n_reviews, t->ts_dev_off, w0, w1, &rev, &dv, &de, &ms);
+        device_ms += ms;
+        if (!table_merge_page(rev, dv, de, mw, hv, he, nc, t->n_reviews, w0, w1, &h->reviews, &h->viol, &h->err))
+          throw std::runtime_error("gk_table_violations: the device's entries do not fit the page");
+        if (h->reviews.size() != t->ts_prefix[w1] - t->ts_prefix[w0]) throw std::runtime_error("gk_table_violations: the page's entries do not add up to the table's index");
+        const uint32_t nx = viol_next_word(t->ts_prefix, w1);
+        if (nx < pw) {
+          next_cursor = table_cursor_pack(t->ts_gen, nx);
+          if (!next_cursor) throw std::runtime_error("gk_table_violations: the position does not fit a cursor");
+        }
+      }
+    }
+    const uint32_t mw = ((uint32_t)h->ids.size() + 63u) / 64u;
+    if ((flags & GK_VIOLATIONS_RENDER) && !h->reviews.empty()) {
+      const size_t n = h->reviews.size();
+      h->result_text.resize(n);
+      size_t n_threads = std::max<size_t>(1, std::min<size_t>(host_cpus(), n));
+      if (const char* ht = getenv("GK_HOST_THREADS")) n_threads = std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, atoi(ht)), n));
+      std::atomic<size_t> next{0};
+      std::mutex err_mu;
+      std::string first_err;
+      auto worker = [&](size_t) {   // one entry per task, handed out in page order
+        for (;;) {
+          const size_t i = next.fetch_add(1);
+          if (i >= n) return;
+          try {
+            h->result_text[i] = table_entry_json(e, t, h->ids, h->reviews[i], h->viol.data() + i * mw, h->err.data() + i * mw);
+          } catch (const std::exception& ex) {
+            std::lock_guard<std::mutex> l(err_mu);
+            if (first_err.empty()) first_err = ex.what()[0] ? ex.what() : "rendering failed";
+            next.store(n);   // (the call fails: the remaining entries are not rendered)
+          }
+        }
+      };
+      HostWorkers::get().run(n_threads, worker);
+      if (!first_err.empty()) return fail(GK_ERR_REGO, first_err);
+      for (const std::string& r : h->result_text) h->results.push_back(r.c_str());
+    }
+    gk_table_violations_out& p = h->pub;
+    const uint64_t total = p.total_entries;
+    memset(&p, 0, sizeof p);
+    p.n_reviews = t->n_reviews; p.n_constraints = (uint32_t)h->ids.size(); p.mask_words = mw;
+    p.constraint_ids = h->ids.data();
+    p.total_entries = total;
+    p.n_entries = (uint32_t)h->reviews.size();
+    p.reviews = h->reviews.data(); p.viol = h->viol.data(); p.err = h->err.data();
+    p.results_json = h->results.empty() ? nullptr : h->results.data();
+    p.beyond_limits = beyond;
+    p.next_cursor = next_cursor;
+    p.device_ms = device_ms;
+    *out = &h.release()->pub;
+    return GK_OK;
+  } catch (const std::exception& ex) { return fail(GK_ERR_DEVICE, ex.what()); }
+}
+
+void gk_table_violations_free(gk_table_violations_out* o) { if (o) delete reinterpret_cast<TableViolationsHolder*>(o); }
 
 // Driver.Query's `constraints` as a sorted id list; GK_ERR_NOT_FOUND for an id that is not loaded
 static int wanted_ids(gk_engine* e, const uint32_t* ids, size_t n, std::vector<uint32_t>* out) {

@@ -391,6 +391,52 @@ class Table:
         self.engine.lib.gk_topk_free(out)
         return res
 
+    def violation_pages(self, page=4096, render=False):
+        """gk_table_violations page by page, for a caller that wants the pages themselves: yields dicts with `ids` (constraint id of every
+        bitmap row), `reviews` / `viol` / `err` as numpy arrays ([n], [n][mask_words], [n][mask_words]), `rows` (per entry, with `render`:
+        gk_query's rows; else None), `total_entries`, `beyond_limits`, `device_ms`, `next_cursor`.  Frees each page."""
+        lib, cursor = self.engine.lib, 0
+        while True:
+            out = C.POINTER(L.gk_table_violations_out)()
+            self.engine._check(lib.gk_table_violations(self.engine.handle, self.handle, cursor, int(page), L.GK_VIOLATIONS_RENDER if render else 0, C.byref(out)))
+            try:
+                o = out.contents
+                n, mw = int(o.n_entries), int(o.mask_words)
+                pg = {"ids": [int(o.constraint_ids[i]) for i in range(o.n_constraints)], "n_reviews": int(o.n_reviews), "mask_words": mw,
+                      "reviews": np.ctypeslib.as_array(o.reviews, (n,)).copy() if n else np.zeros(0, np.uint32),
+                      "viol": np.ctypeslib.as_array(o.viol, (n * mw,)).reshape(n, mw).copy() if n * mw else np.zeros((n, mw), np.uint64),
+                      "err": np.ctypeslib.as_array(o.err, (n * mw,)).reshape(n, mw).copy() if n * mw else np.zeros((n, mw), np.uint64),
+                      "rows": [json.loads(o.results_json[i].decode()) for i in range(n)] if render and n else None,
+                      "total_entries": int(o.total_entries), "beyond_limits": int(o.beyond_limits), "device_ms": float(o.device_ms),
+                      "next_cursor": int(o.next_cursor)}
+                cursor = pg["next_cursor"]
+            finally:
+                lib.gk_table_violations_free(out)
+            yield pg
+            if not cursor:
+                return
+
+    def violations(self, page=4096, render=False):
+        """Every review with at least one result in the most recent collected eval(), ascending, from gk_table_violations -- also after
+        eval(download=False): the bitmaps never come back.  Yields (review, [bitmap rows violated], [bitmap rows autorejected]) and,
+        with `render`, a fourth member: the entry's rows in gk_query's JSON.  An eval() / launch() or a policy change while the
+        generator is open makes its next page fail (EngineError, GK_ERR_INVALID).  self.beyond_limits: reviews beyond the device's
+        limits that no host evaluation answered."""
+        for pg in self.violation_pages(page, render):
+            self.beyond_limits = pg["beyond_limits"]
+            for i, r in enumerate(pg["reviews"]):
+                sets = []
+                for arr in (pg["viol"], pg["err"]):
+                    got = []
+                    for w in range(pg["mask_words"]):
+                        m = int(arr[i, w])
+                        while m:
+                            low = m & -m
+                            got.append(w * 64 + low.bit_length() - 1)
+                            m ^= low
+                    sets.append(got)
+                yield (int(r), sets[0], sets[1], pg["rows"][i]) if render else (int(r), sets[0], sets[1])
+
     def stats(self):
         """host-side cost of building the table (gk_table_get_stats) as a dict"""
         st = L.gk_table_stats()
@@ -1209,25 +1255,97 @@ class Client:
         fills Metadata["details"] for them is unpinned: DESIGN.md section 2)."""
         info = self._active(AUDIT_EP)
         for path, _viol, _err, rows in self.driver.ResidentViolations(page, render=True):
-            obj = self.cached[path]
-            g, ver, kind = obj_gvk(obj)
-            md = obj.get("metadata") or {}
-            for v in rows:
-                if v["constraint"] not in info:
-                    continue
-                c, ea, scoped = info[v["constraint"]]
-                cg, cver, ckind = obj_gvk(c)
-                cmd = c.get("metadata") or {}
-                ann = {k: a for k, a in (cmd.get("annotations") or {}).items() if k != "kubectl.kubernetes.io/last-applied-configuration"}
-                msg = {"id": timestamp, "eventType": "violation_audited", "group": cg, "version": cver, "kind": ckind, "name": cmd.get("name", "") or "",
-                       "namespace": cmd.get("namespace", "") or "", "message": truncate_string(v["msg"], msg_size), "enforcementAction": ea,
-                       "enforcementActions": list(scoped or ()), "constraintAnnotations": ann, "resourceGroup": g, "resourceAPIVersion": ver,
-                       "resourceKind": kind, "resourceNamespace": md.get("namespace", "") or "", "resourceName": md.get("name", "") or "",
-                       "resourceLabels": dict(md.get("labels") or {})}
-                msg = {k: x for k, x in msg.items() if x not in ("", {}, [])}
-                if "details" in v and not v.get("autoreject"):
-                    msg["details"] = v["details"]
-                yield msg
+            yield from self._violation_msgs(timestamp, self.cached[path], rows, info, msg_size)
+
+    @staticmethod
+    def _violation_msgs(timestamp, obj, rows, info, msg_size):
+        """violationMsg's dict for every row (gk_query's format) of one audited object whose constraint is in `info` (_active)"""
+        g, ver, kind = obj_gvk(obj)
+        md = obj.get("metadata") or {}
+        for v in rows:
+            if v["constraint"] not in info:
+                continue
+            c, ea, scoped = info[v["constraint"]]
+            cg, cver, ckind = obj_gvk(c)
+            cmd = c.get("metadata") or {}
+            ann = {k: a for k, a in (cmd.get("annotations") or {}).items() if k != "kubectl.kubernetes.io/last-applied-configuration"}
+            msg = {"id": timestamp, "eventType": "violation_audited", "group": cg, "version": cver, "kind": ckind, "name": cmd.get("name", "") or "",
+                   "namespace": cmd.get("namespace", "") or "", "message": truncate_string(v["msg"], msg_size), "enforcementAction": ea,
+                   "enforcementActions": list(scoped or ()), "constraintAnnotations": ann, "resourceGroup": g, "resourceAPIVersion": ver,
+                   "resourceKind": kind, "resourceNamespace": md.get("namespace", "") or "", "resourceName": md.get("name", "") or "",
+                   "resourceLabels": dict(md.get("labels") or {})}
+            msg = {k: x for k, x in msg.items() if x not in ("", {}, [])}
+            if "details" in v and not v.get("autoreject"):
+                msg["details"] = v["details"]
+            yield msg
+
+    def _audit_stream_rows(self, objs, namespaces, page):
+        """The list-based audit's stream: ONE table of `objs` (resident, audit process), ONE evaluation, then gk_table_violations' pages.
+        Yields, in ascending index into objs, (index, rows in gk_query's JSON) for the objects that have results and (index, ReviewFailure)
+        for those ReviewBatch fails closed on: rejected by HandleReview, or beyond the engine's limits with no host evaluation's answer."""
+        rins, idx = [], []
+        for i, o in enumerate(objs):
+            r = to_review_in(o, namespaces[i] if namespaces else None)
+            if r is not None:
+                rins.append(r)
+                idx.append(i)
+        if not rins:
+            return
+        table = self.driver.engine.create_table(rins, resident=True, process="audit")
+        try:
+            ev = table.eval()   # (downloading: only such an evaluation completes over-limit reviews on the host, and says which stay refused)
+            failed = {}
+            for k, st in enumerate(table.statuses):
+                if st not in (L.GK_OK, L.GK_REVIEW_EXCLUDED):
+                    failed[k] = ReviewFailure(idx[k], "review %d rejected by HandleReview" % idx[k])   # ErrReview
+            for k in ev.too_big_reviews():
+                failed[k] = ReviewFailure(idx[k], str(LimitError("review %d" % idx[k])), LimitError("review %d" % idx[k]))
+            del ev
+            pending = sorted(failed)
+            at = 0
+            for r, _viol, _err, rows in table.violations(page, render=True):
+                while at < len(pending) and pending[at] <= r:
+                    yield idx[pending[at]], failed[pending[at]]
+                    at += 1
+                if r not in failed:
+                    yield idx[r], rows
+            for k in pending[at:]:
+                yield idx[k], failed[k]
+        finally:
+            table.free()
+
+    def AuditStream(self, objs, namespaces=None, page=4096):
+        """The list-based audit (pkg/audit/manager.go:519-551, 667-776) for a caller that acts on every single result (:927-939): a
+        generator of (index into objs, [Result]) over the objects that HAVE results at the audit enforcement point, in ascending index,
+        from one table, one evaluation and gk_table_violations -- no bitmap is walked on the host, nothing is rendered for an object
+        without results.  The Results are what ReviewBatch(process="audit") gives for the object, in its order; an object ReviewBatch
+        turns into a ReviewFailure is yielded as (index, that failure), never left out."""
+        info = self._active(AUDIT_EP)
+        for i, rows in self._audit_stream_rows(objs, namespaces, page):
+            if isinstance(rows, ReviewFailure):
+                yield i, rows
+                continue
+            res = []
+            # (ReviewBatch's order: the autoreject results first, then the violations, each by constraint id)
+            for v in sorted((v for v in rows if v.get("autoreject")), key=lambda v: v["constraint"]):
+                if v["constraint"] in info:
+                    c, ea, scoped = info[v["constraint"]]
+                    res.append(Result(v["msg"], c, {}, ea, scoped))
+            for v in sorted((v for v in rows if not v.get("autoreject")), key=lambda v: v["constraint"]):
+                if v["constraint"] in info:
+                    c, ea, scoped = info[v["constraint"]]
+                    res.append(Result(v["msg"], c, v.get("details", {}), ea, scoped))
+            if res:
+                yield i, res
+
+    def AuditMessages(self, objs, timestamp, namespaces=None, page=4096, msg_size=256):
+        """AuditViolationMessages for the list-based audit: one violationMsg-shaped dict per Result of `objs`, from AuditStream's table
+        and stream.  An object the engine fails closed on raises its ReviewFailure."""
+        info = self._active(AUDIT_EP)
+        for i, rows in self._audit_stream_rows(objs, namespaces, page):
+            if isinstance(rows, ReviewFailure):
+                raise rows
+            yield from self._violation_msgs(timestamp, review_object(objs[i]), rows, info, msg_size)
 
     def AuditReportFromCache(self, limit=20, msg_size=256):
         """What an audit run over the resident set writes into the constraints' status (pkg/audit/manager.go:885-941 behind auditFromCache):

@@ -409,6 +409,37 @@ typedef struct {
 } gk_violations_out;
 int gk_resident_violations(gk_engine* e, uint64_t cursor, uint32_t max_objects, uint32_t flags, gk_violations_out** out);
 void gk_violations_free(gk_violations_out* o);
+/* The same for the list-based audit (gk_table_create / gk_table_create_spool + gk_table_eval): gk_table_violations names every review
+ * of the table that has at least one result in the table's most recent collected evaluation -- it evaluates nothing itself, and works
+ * behind GK_EVAL_NO_DOWNLOAD and GK_EVAL_DEVICE_ONLY evaluations as well, so an audit never has to bring the bitmaps back.  The device
+ * compacts the violation AND the autoreject bitmaps of all plan groups into (review, viol mask, err mask) entries; the pairs the host
+ * evaluation of over-limit reviews added are merged in on the host.  Bit c of an entry's masks = bit `review` of row c of what a
+ * downloading, host-completing gk_table_eval of the table returns in gk_eval_out.viol / .err; a review has an entry iff one of those
+ * bits is set.  Device bits of a review beyond the device's limits are never reported: the host evaluation of the SAME evaluation
+ * answered it, or it counts in beyond_limits (after GK_EVAL_NO_DOWNLOAD / GK_EVAL_DEVICE_ONLY: every such review).
+ * Pages: a page is the longest run of whole 64-review bitmap words whose entries fit in max_entries (below 64 counts as 64; at least
+ * one word).  cursor 0 begins a stream; next_cursor continues it and is opaque.  Every launch that writes the table's result buffers
+ * (an evaluation -- enqueued or collected --, gk_table_verify, a sharded sweep) and every policy change ends the stream: a cursor from
+ * before is refused with GK_ERR_INVALID ("... start again with cursor 0"), never answered from other bitmaps.  Also GK_ERR_INVALID: a
+ * table that was never evaluated or whose policies changed since, GK_EVAL_ASYNC launches still to be collected, a table set up as a
+ * shard, GK_VIOLATIONS_RENDER on a table without GK_TABLE_KEEP_DOCS / GK_TABLE_KEEP_TEXT.  With GK_VIOLATIONS_RENDER, results_json[i]
+ * is a JSON array of rows in gk_query's format, in ascending bitmap row: for an err bit gk_render_error's row, for a viol bit
+ * gk_render's rows, each with its "constraint" id; rendering runs on the host workers (GK_HOST_THREADS). */
+typedef struct {
+  uint32_t n_reviews, n_constraints, mask_words;   /* mask_words = ceil(n_constraints / 64) */
+  const uint32_t* constraint_ids;   /* [n_constraints], bitmap-row order of the evaluation streamed */
+  uint64_t total_entries;           /* entries of the WHOLE stream, on every page */
+  uint32_t n_entries;               /* on this page */
+  const uint32_t* reviews;          /* [n_entries] review indices, strictly ascending */
+  const uint64_t* viol;             /* [n_entries][mask_words] */
+  const uint64_t* err;              /* [n_entries][mask_words] autoreject */
+  const char* const* results_json;  /* [n_entries] with GK_VIOLATIONS_RENDER, else NULL */
+  uint64_t beyond_limits;           /* reviews whose device too_big bit is set and that no host evaluation answered */
+  uint64_t next_cursor;             /* 0: last page */
+  float device_ms;                  /* HIP-event time of this call's kernels */
+} gk_table_violations_out;
+int gk_table_violations(gk_engine* e, gk_table* t, uint64_t cursor, uint32_t max_entries, uint32_t flags, gk_table_violations_out** out);
+void gk_table_violations_free(gk_table_violations_out* o);
 /* results of one swept object, in gk_query's JSON; GK_ERR_NOT_FOUND when the object is unknown or its answer is stale */
 int gk_resident_review(gk_engine* e, const char* const* path, size_t npath, char** results_json);
 /* the same for a caller that matched itself (gk_query_ex2's arguments).  With GK_QUERY_PRE_MATCHED the sweep's bitmaps -- match AND
