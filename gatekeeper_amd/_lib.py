@@ -34,6 +34,9 @@ GK_EVAL_WANT_MATCH, GK_EVAL_NO_DOWNLOAD, GK_EVAL_WANT_LIST, GK_EVAL_ASYNC, GK_EV
 GK_EVAL_DEVICE_ONLY = 128
 GK_SWEEP_RESULT_TOTALS = 1
 GK_VIOLATIONS_RENDER = 1
+GK_CHANGES_RENDER = 1
+GK_CHANGES_RESTART = 2
+GK_CHANGE_GONE = 1
 
 EXPORTS = [
     "gk_engine_create", "gk_engine_destroy", "gk_last_error", "gk_version", "gk_template_add", "gk_template_remove",
@@ -41,7 +44,7 @@ EXPORTS = [
     "gk_table_eval", "gk_eval_free", "gk_render", "gk_render_error", "gk_free", "gk_dump", "gk_table_review_words", "gk_table_topk", "gk_topk_free",
     "gk_table_totals", "gk_totals_free", "gk_table_get_stats", "gk_batcher_start", "gk_batcher_stop", "gk_query", "gk_query_ex", "gk_query_ex2",
     "gk_resident_sweep", "gk_sweep_free", "gk_resident_review", "gk_resident_review_ex", "gk_resident_audit", "gk_audit_free",
-    "gk_resident_violations", "gk_violations_free", "gk_table_violations", "gk_table_violations_free", "gk_table_verify", "gk_verify_free", "gk_resident_verify",
+    "gk_resident_violations", "gk_violations_free", "gk_resident_changes", "gk_changes_free", "gk_table_violations", "gk_table_violations_free", "gk_table_verify", "gk_verify_free", "gk_resident_verify",
     "gk_comm_unique_id", "gk_comm_init", "gk_comm_destroy", "gk_comm_info", "gk_table_sweep_sharded", "gk_shard_free",
     "gk_jit_quiesce", "gk_jit_cache_stats", "gk_jit_cache_dir", "gk_jit_cache_drop_memory", "gk_host_cpus", "gk_table_create_spool", "gk_spool_info_free", "gk_debug_set",
     # include/gksynth.h (bench / test plumbing)
@@ -114,6 +117,15 @@ class gk_violations_out(C.Structure):
                 ("constraint_ids", C.POINTER(C.c_uint32)), ("total_objects", C.c_uint64), ("n_entries", C.c_uint32), ("paths", C.POINTER(C.c_char_p)),
                 ("viol", C.POINTER(C.c_uint64)), ("err", C.POINTER(C.c_uint64)), ("results_json", C.POINTER(C.c_char_p)),
                 ("beyond_limits", C.c_uint64), ("next_cursor", C.c_uint64)]
+
+
+class gk_changes_out(C.Structure):
+    _fields_ = [("n_objects", C.c_uint64), ("n_constraints", C.c_uint32), ("n_chunks", C.c_uint32), ("mask_words", C.c_uint32),
+                ("constraint_ids", C.POINTER(C.c_uint32)), ("reset", C.c_uint32), ("total_entries", C.c_uint64), ("n_entries", C.c_uint32),
+                ("paths", C.POINTER(C.c_char_p)), ("viol", C.POINTER(C.c_uint64)), ("err", C.POINTER(C.c_uint64)),
+                ("was_viol", C.POINTER(C.c_uint64)), ("was_err", C.POINTER(C.c_uint64)), ("entry_flags", C.POINTER(C.c_uint32)),
+                ("results_json", C.POINTER(C.c_char_p)), ("beyond_limits", C.c_uint64), ("next_cursor", C.c_uint64), ("device_ms", C.c_float),
+                ("baseline_bytes", C.c_uint64)]
 
 
 class gk_table_violations_out(C.Structure):
@@ -271,6 +283,9 @@ def load(hostemu: bool | None = None):
     lib.gk_resident_violations.argtypes = [vp, C.c_uint64, u32, u32, C.POINTER(C.POINTER(gk_violations_out))]
     lib.gk_violations_free.argtypes = [C.POINTER(gk_violations_out)]
     lib.gk_violations_free.restype = None
+    lib.gk_resident_changes.argtypes = [vp, C.c_uint64, u32, u32, C.POINTER(C.POINTER(gk_changes_out))]
+    lib.gk_changes_free.argtypes = [C.POINTER(gk_changes_out)]
+    lib.gk_changes_free.restype = None
     lib.gk_table_violations.argtypes = [vp, vp, C.c_uint64, u32, u32, C.POINTER(C.POINTER(gk_table_violations_out))]
     lib.gk_table_violations_free.argtypes = [C.POINTER(gk_table_violations_out)]
     lib.gk_table_violations_free.restype = None

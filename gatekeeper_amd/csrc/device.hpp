@@ -95,6 +95,27 @@ void dev_viol_index(const DevTable* t, uint32_t nc, uint32_t n_reviews, const st
                     std::vector<uint32_t>* cnt, std::vector<uint64_t>* any = nullptr);
 void dev_viol_entries(const DevTable* t, uint32_t nc, uint32_t n_reviews, const std::vector<uint64_t>& shown, uint64_t shown_gen, uint32_t w0, uint32_t w1,
                       std::vector<uint32_t>* reviews, std::vector<uint64_t>* masks);
+// resident-set changes stream (gk_resident_changes): what differs between the most recent evaluation's violation bitmap read under `shown`
+// and the BASELINE of the table (view) -- a copy of that bitmap and of the mask it was read under, made by dev_delta_keep (device to
+// device, allocated at the first call) and held beside the table until dev_delta_drop or the table goes away.  A review that is not set
+// in a side's mask counts as all zero on that side.  Without use_base, or when the table has no baseline, the baseline reads as zero
+// (no buffer is filled for that); a baseline of another row count or layout makes both entries throw.  dev_delta_has: a baseline for
+// `nc` rows of this table is there; dev_delta_bytes: what it holds on the device.
+// dev_delta_index: changed[w] = the reviews of bitmap word w with a differing bit in at least one row, cnt[w] = their number.
+// dev_delta_entries: the entries of the words [w0, w1), reviews ascending, `now` / `was` = [entries][ceil(nc / 64)] masks of the two
+// sides, bit r = row r.  `off` is the page's slice [w1 - w0 + 1] of the exclusive prefix sum that places the entries (the caller keeps
+// the index); `extra`, when given, [w1 - w0] words of reviews that get an entry whatever this table's bitmaps say -- a caller that
+// merges several sources per word passes the merged words, so that every source emits the same reviews.  It throws when the index does
+// not fit the bitmaps.  *ms: HIP-event time of the call's kernels (the CPU stand-in: 0).  The mask is dev_audit_select's device copy.
+void dev_delta_keep(const DevTable* t, uint32_t nc, uint32_t n_reviews, const std::vector<uint64_t>& shown, uint64_t shown_gen);
+bool dev_delta_has(const DevTable* t, uint32_t nc);
+uint64_t dev_delta_bytes(const DevTable* t);
+void dev_delta_drop(const DevTable* t);
+void dev_delta_index(const DevTable* t, uint32_t nc, uint32_t n_reviews, const std::vector<uint64_t>& shown, uint64_t shown_gen, bool use_base,
+                     std::vector<uint32_t>* cnt, std::vector<uint64_t>* changed, float* ms);
+void dev_delta_entries(const DevTable* t, uint32_t nc, uint32_t n_reviews, const std::vector<uint64_t>& shown, uint64_t shown_gen, bool use_base, uint32_t w0,
+                       uint32_t w1, const std::vector<uint32_t>& off, const std::vector<uint64_t>* extra, std::vector<uint32_t>* reviews,
+                       std::vector<uint64_t>* now, std::vector<uint64_t>* was, float* ms);
 // table violation stream (gk_table_violations): every review with a bit in at least one row of the violation OR the autoreject bitmap of
 // the most recent evaluation, over ALL plan groups at once.  A side is what one group evaluated into (the table or a view of it), its
 // rows and its first row among all constraints; sides without rows are skipped.  Reviews with a too_big bit in any side are masked

@@ -34,6 +34,7 @@
 #include "verify_merge.hpp"
 #include "table_stream.hpp"
 #include "viol_stream.hpp"
+#include "delta_stream.hpp"
 
 using namespace gk;
 
@@ -344,7 +345,20 @@ struct gk_engine {
     std::vector<uint64_t> vs_prefix;
     std::vector<uint32_t> vs_host_slots;
     uint64_t vs_plan_gen = 0, vs_shown_gen = 0;
-    gk_eval_out* ev = nullptr;        // bitmaps of the chunk's most recent evaluation
+    // gk_resident_changes.  The BASELINE of the chunk (cs_has_base: the chunk existed when the last changes stream was handed out
+    // completely): the device keeps a copy of every plan group's violation bitmap and of the shown mask beside the group's side
+    // (dev_delta_keep); here the mask's host copy and the pairs no device bitmap carries -- autoreject pairs, violating pairs the host
+    // evaluator completed -- as sorted (slot, row) lists under that mask.  The index of the stream (kept like vs_*, and while the
+    // baseline cs_base_gen and the reset state cs_reset it was built against stand): cs_changed = the slots with an entry per bitmap
+    // word over ALL sources, cs_prefix its exclusive prefix sum, cs_now_* = the pairs as they are now, cs_merged = an entry may come
+    // from more than one source (several plan groups, host pairs that differ): every group then emits the merged words' slots.
+    bool cs_has_base = false;
+    std::vector<uint64_t> cs_base_shown;
+    std::vector<std::pair<uint32_t, uint32_t>> cs_base_err, cs_base_hviol, cs_now_err, cs_now_hviol;
+    std::vector<uint64_t> cs_prefix, cs_changed;
+    bool cs_merged = false, cs_reset = false;
+    uint64_t cs_plan_gen = 0, cs_shown_gen = 0, cs_base_gen = 0;
+    gk_eval_out* ev = nullptr;       // bitmaps of the chunk's most recent evaluation
     uint64_t plan_gen = 0;            // ... and the plan generation they belong to
     uint64_t n_live = 0;
   };
@@ -363,6 +377,14 @@ struct gk_engine {
     uint64_t set_gen = 0, compactions = 0;
     uint32_t vs_gen = 0;
     uint64_t vs_set_gen = 0, vs_compactions = 0, vs_plan_gen = 0, vs_excl_gen = 0;
+    // gk_resident_changes: stream generation fields of its own (the two streams do not invalidate each other), the reset state of the
+    // stream cs_gen stands for, and the baseline: cs_base_gen counts the commits (0: none yet), cs_base_compactions / cs_base_ids say
+    // what it is comparable with (ids: per plan group the constraint ids in bitmap-row order)
+    uint32_t cs_gen = 0;
+    uint64_t cs_set_gen = 0, cs_compactions = 0, cs_plan_gen = 0, cs_excl_gen = 0;
+    bool cs_reset = false;
+    uint64_t cs_base_gen = 0, cs_base_compactions = 0, cs_stream_base_gen = 0;
+    std::vector<std::vector<uint32_t>> cs_base_ids;
   } resident;
   // ---- admission micro-batcher (gk_query): concurrent single-review calls coalesced into one table + one launch
   struct BatchResult;   // one evaluated batch: table + bitmaps, shared by its requests until the last one has rendered
@@ -1732,6 +1754,7 @@ void gk_table_free(gk_table* t) {
     dev_plan_free(s.vtwin);
     dev_verify_forget(s.dev);
     dev_tviol_forget(s.dev);
+    dev_delta_drop(s.dev);
     dev_table_free(s.dev);
   }
   delete t;
@@ -3177,6 +3200,40 @@ struct ViolationsHolder {
 };
 const char* const k_stream_moved = "the resident set or the policies changed since the stream began: start again with cursor 0";
 
+// What both resident streams render for a page (GK_VIOLATIONS_RENDER / GK_CHANGES_RENDER): gk_resident_review's answer for the objects
+// of the page entries listed in `todo` (indices into slots, ascending), on the host workers (GK_HOST_THREADS), one object per task
+// handed out in page order; text is [slots].  GK_OK, or the first failure's status with its text in *error (the remaining objects are
+// then not rendered).  R.mu held.
+int resident_render_page(gk_engine* e, const gk_engine::ResChunk& c, const std::vector<uint32_t>& slots, const std::vector<size_t>& todo,
+                         std::vector<std::string>* text, std::string* error) {
+  text->resize(slots.size());
+  if (todo.empty()) return GK_OK;
+  size_t n_threads = std::max<size_t>(1, std::min<size_t>(host_cpus(), todo.size()));
+  if (const char* ht = getenv("GK_HOST_THREADS")) n_threads = std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, atoi(ht)), todo.size()));
+  std::atomic<size_t> next{0};
+  std::mutex err_mu;
+  int first_status = GK_OK;
+  auto worker = [&](size_t) {
+    for (;;) {
+      const size_t k = next.fetch_add(1);
+      if (k >= todo.size()) return;
+      const size_t i = todo[k];
+      std::string err;
+      int st = GK_OK;
+      try {
+        if (!resident_answer(e, c.obj_of_slot[slots[i]], &(*text)[i], &st, &err, true)) { st = GK_ERR_INVALID; err = k_stream_moved; }
+      } catch (const std::exception& ex) { st = GK_ERR_REGO; err = ex.what(); }
+      if (st != GK_OK) {
+        std::lock_guard<std::mutex> l(err_mu);
+        if (first_status == GK_OK) { first_status = st; *error = err; }
+        next.store(todo.size());
+      }
+    }
+  };
+  HostWorkers::get().run(n_threads, worker);
+  return first_status;
+}
+
 // The index of one chunk: per plan group the device counts the shown reviews with a bit per bitmap word (dev_viol_index) and keeps the
 // prefix sum that places its entries.  Where nothing else can add an entry -- one group, no autoreject bit, no host-evaluated
 // violation: the common state -- those counts ARE the index and 4 bytes per word come back.  Otherwise an object may be named by
@@ -3346,31 +3403,11 @@ int gk_resident_violations(gk_engine* e, uint64_t cursor, uint32_t max_objects, 
       for (size_t off : at) h->paths.push_back(a.data() + off);   // (after the last append: the arena no longer moves)
     }
     if ((flags & GK_VIOLATIONS_RENDER) && !slots.empty()) {
-      h->result_text.resize(slots.size());
-      size_t n_threads = std::max<size_t>(1, std::min<size_t>(host_cpus(), slots.size()));
-      if (const char* ht = getenv("GK_HOST_THREADS")) n_threads = std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, atoi(ht)), slots.size()));
-      std::atomic<size_t> next{0};
-      std::mutex err_mu;
-      std::string first_err;
-      int first_status = GK_OK;
-      auto worker = [&](size_t) {   // one object per task, handed out in page order
-        for (;;) {
-          const size_t i = next.fetch_add(1);
-          if (i >= slots.size()) return;
-          std::string err;
-          int st = GK_OK;
-          try {
-            if (!resident_answer(e, pc->obj_of_slot[slots[i]], &h->result_text[i], &st, &err, true)) { st = GK_ERR_INVALID; err = k_stream_moved; }
-          } catch (const std::exception& ex) { st = GK_ERR_REGO; err = ex.what(); }
-          if (st != GK_OK) {
-            std::lock_guard<std::mutex> l(err_mu);
-            if (first_status == GK_OK) { first_status = st; first_err = err; }
-            next.store(slots.size());   // (the call fails: the remaining objects are not rendered)
-          }
-        }
-      };
-      HostWorkers::get().run(n_threads, worker);
-      if (first_status != GK_OK) return fail(first_status, first_err);
+      std::vector<size_t> todo(slots.size());   // every entry has a result
+      for (size_t i = 0; i < todo.size(); i++) todo[i] = i;
+      std::string err;
+      const int st = resident_render_page(e, *pc, slots, todo, &h->result_text, &err);
+      if (st != GK_OK) return fail(st, err);
       for (const std::string& r : h->result_text) h->results.push_back(r.c_str());
     }
     gk_violations_out& p = h->pub;
@@ -3390,6 +3427,274 @@ int gk_resident_violations(gk_engine* e, uint64_t cursor, uint32_t max_objects, 
 }
 
 void gk_violations_free(gk_violations_out* o) { if (o) delete reinterpret_cast<ViolationsHolder*>(o); }
+
+// ---- gk_resident_changes: what differs in that stream's answer since the last changes stream that was handed out completely
+// (viol_stream.hpp: pages and cursors; delta_stream.hpp: the pairs only the host knows)
+namespace {
+struct ChangesHolder {
+  gk_changes_out pub;   // first member
+  std::vector<uint32_t> ids, entry_flags;
+  std::vector<uint64_t> viol, err, was_viol, was_err;
+  std::string path_arena;
+  std::vector<std::string> result_text;
+  std::vector<const char*> paths, results;
+};
+
+// per plan group the constraint ids in bitmap-row order: what a baseline is comparable with (plan_rw held)
+std::vector<std::vector<uint32_t>> changes_group_ids(const gk_engine* e) {
+  std::vector<std::vector<uint32_t>> v;
+  for (const auto& g : e->groups) v.push_back(g->ids);
+  return v;
+}
+
+// The index of one chunk against its baseline (reset: against nothing).  Per plan group the device marks the shown-now or shown-then
+// slots whose bits differ (dev_delta_index); the pairs no device bitmap carries are listed as they are now and compared with the
+// baseline's lists.  A slot counts once whatever its sources: the words are ORed before they are counted.  R.mu and plan_rw (shared) held.
+void resident_delta_index(gk_engine* e, gk_engine::ResChunk& c, const std::vector<uint32_t>& ids, bool reset, uint64_t base_gen, float* ms) {
+  gk_table* t = c.table;
+  const gk_eval_out* ev = c.ev;
+  const uint32_t pw = (t->n_reviews + 63u) / 64u, nt = ev->n_tiles, rows = std::min<uint32_t>(ev->n_constraints, (uint32_t)ids.size());
+  const bool use_base = !reset && c.cs_has_base;
+  auto shown_bit = [&](uint32_t slot) { return slot / 64 < c.shown.size() && ((c.shown[slot / 64] >> (slot % 64)) & 1ull); };
+  c.cs_now_err.clear(); c.cs_now_hviol.clear();
+  for (uint32_t w = 0; w < pw && w < nt && w < c.shown.size(); w++) {   // (word by word, slot by slot: the list comes out in order)
+    uint64_t any = 0;
+    for (uint32_t row = 0; row < rows; row++) any |= ev->err[(size_t)row * nt + w];
+    for (uint64_t m = any & c.shown[w]; m; m &= m - 1) {
+      const uint32_t b = (uint32_t)__builtin_ctzll(m), slot = w * 64u + b;
+      if (slot >= t->n_reviews) break;
+      for (uint32_t row = 0; row < rows; row++)
+        if ((ev->err[(size_t)row * nt + w] >> b) & 1ull) c.cs_now_err.emplace_back(slot, row);
+    }
+  }
+  {
+    std::lock_guard<std::mutex> hl(t->host_mu);
+    if (t->host_ids == ids)
+      for (auto& hp : t->host_viol) if (hp.first < rows && hp.second < t->n_reviews && shown_bit(hp.second)) c.cs_now_hviol.emplace_back(hp.second, hp.first);
+  }
+  delta_pairs_sort(&c.cs_now_hviol);
+  static const std::vector<DeltaPair> none;
+  const std::vector<uint32_t> host_slots = viol_merge_slots(delta_pairs_changed(c.cs_now_err, use_base ? c.cs_base_err : none),
+                                                            delta_pairs_changed(c.cs_now_hviol, use_base ? c.cs_base_hviol : none));
+  std::vector<uint64_t> changed(pw, 0), a;
+  for (uint32_t slot : host_slots) if (slot < t->n_reviews) changed[slot / 64] |= 1ull << (slot % 64);
+  c.cs_merged = !host_slots.empty() || (e->groups.size() > 1 && t->sides.size() > 1);
+  std::vector<uint32_t> n;
+  each_group(e, t, [&](const GroupAt& g) {
+    if (g.nc == 0) return;
+    float m = 0;
+    dev_delta_index(g.side.dev, g.nc, t->n_reviews, c.shown, c.shown_gen, use_base, &n, &a, &m);
+    if (n.size() != pw || a.size() != pw) throw std::runtime_error("dev_delta_index: wrong size");
+    for (uint32_t w = 0; w < pw; w++) changed[w] |= a[w];
+    *ms += m;
+  });
+  c.cs_prefix.assign((size_t)pw + 1, 0);
+  for (uint32_t w = 0; w < pw; w++) c.cs_prefix[w + 1] = c.cs_prefix[w] + (uint64_t)__builtin_popcountll(changed[w]);
+  c.cs_changed.swap(changed);
+  c.cs_plan_gen = c.plan_gen; c.cs_shown_gen = c.shown_gen; c.cs_base_gen = base_gen; c.cs_reset = reset;
+}
+}  // namespace
+
+int gk_resident_changes(gk_engine* e, uint64_t cursor, uint32_t max_objects, uint32_t flags, gk_changes_out** out) {
+  if (!e || !out) return fail(GK_ERR_INVALID, "NULL argument");
+  try {
+    gk_engine::Resident& R = e->resident;
+    std::lock_guard<std::mutex> rl(R.mu);
+    std::unique_ptr<ChangesHolder> h(new ChangesHolder());
+    if (cursor == 0) {   // a stream begins: the set is brought up to date as by gk_resident_sweep
+      uint64_t flattened = 0;
+      auto t1 = std::chrono::steady_clock::now();
+      int rc = resident_update(e, &flattened, &t1, &h->ids);
+      if (rc != GK_OK) return rc;
+      R.swept = true;
+    } else {
+      if (!R.swept || R.cs_gen == 0 || R.set_gen != R.cs_set_gen || R.compactions != R.cs_compactions) return fail(GK_ERR_INVALID, k_stream_moved);
+      { std::shared_lock<std::shared_mutex> l(e->mu); if (e->excluder_gen != R.cs_excl_gen) return fail(GK_ERR_INVALID, k_stream_moved); }
+      if (!R.chunks.empty()) h->ids.assign(R.chunks[0].ev->constraint_ids, R.chunks[0].ev->constraint_ids + R.chunks[0].ev->n_constraints);
+    }
+    const uint32_t nc = (uint32_t)h->ids.size(), mw = (nc + 63u) / 64u;
+    uint64_t beyond = 0, total = 0, next_cursor = 0;
+    float device_ms = 0;
+    std::vector<uint32_t> slots;
+    uint32_t page_chunk = 0;
+    bool reset = false;
+    {
+      std::shared_lock<std::shared_mutex> pl(e->plan_rw);
+      if (cursor == 0) {
+        for (auto& c : R.chunks)
+          if (e->plan_dirty || c.plan_gen != e->plan_gen) return fail(GK_ERR_DEVICE, "the policies changed while gk_resident_changes ran: call it again");
+        // is there a baseline these bitmaps can be compared with?
+        reset = R.cs_base_gen == 0 || (flags & GK_CHANGES_RESTART) || R.compactions != R.cs_base_compactions || changes_group_ids(e) != R.cs_base_ids;
+        for (auto& c : R.chunks) {
+          if (reset || !c.cs_has_base) continue;
+          each_group(e, c.table, [&](const GroupAt& g) { if (g.nc && !dev_delta_has(g.side.dev, g.nc)) reset = true; });   // (a side that lost its copy)
+        }
+        for (auto& c : R.chunks)
+          if (c.cs_prefix.empty() || c.cs_plan_gen != c.plan_gen || c.cs_shown_gen != c.shown_gen || c.cs_base_gen != R.cs_base_gen || c.cs_reset != reset)
+            resident_delta_index(e, c, h->ids, reset, R.cs_base_gen, &device_ms);
+        const uint64_t plan_gen = e->plan_gen, excl_gen = R.chunks.empty() ? 0 : R.chunks[0].excl_gen;
+        if (R.cs_gen == 0 || R.cs_set_gen != R.set_gen || R.cs_compactions != R.compactions || R.cs_plan_gen != plan_gen || R.cs_excl_gen != excl_gen ||
+            R.cs_reset != reset || R.cs_stream_base_gen != R.cs_base_gen) {
+          R.cs_gen = viol_next_gen(R.cs_gen);
+          R.cs_set_gen = R.set_gen; R.cs_compactions = R.compactions; R.cs_plan_gen = plan_gen; R.cs_excl_gen = excl_gen;
+          R.cs_reset = reset; R.cs_stream_base_gen = R.cs_base_gen;
+        }
+      } else {
+        if (e->plan_dirty || e->plan_gen != R.cs_plan_gen || R.cs_stream_base_gen != R.cs_base_gen) return fail(GK_ERR_INVALID, k_stream_moved);
+        reset = R.cs_reset;
+        for (auto& c : R.chunks)
+          if (!c.ev || c.plan_gen != e->plan_gen || c.cs_prefix.empty() || c.cs_plan_gen != c.plan_gen || c.cs_shown_gen != c.shown_gen || c.excl_gen != R.cs_excl_gen ||
+              c.cs_base_gen != R.cs_base_gen || c.cs_reset != reset)
+            return fail(GK_ERR_INVALID, k_stream_moved);
+      }
+      std::vector<uint32_t> chunk_words;
+      for (auto& c : R.chunks) {
+        chunk_words.push_back((uint32_t)(c.cs_prefix.size() - 1));
+        total += c.cs_prefix.back();
+        beyond += shown_beyond(c);
+      }
+      // where the page begins: the cursor's word, or the first word of the set that has entries
+      ViolCursor at;
+      bool have = false;
+      if (cursor != 0) {
+        if (!viol_cursor_check(cursor, R.cs_gen, chunk_words, &at)) return fail(GK_ERR_INVALID, k_stream_moved);
+        if (viol_next_word(R.chunks[at.chunk].cs_prefix, at.word) != at.word) return fail(GK_ERR_INVALID, k_stream_moved);   // (no page begins at a word without entries)
+        have = true;
+      } else {
+        at.gen = R.cs_gen;
+        for (uint32_t ci = 0; ci < R.chunks.size() && !have; ci++) {
+          const uint32_t w = viol_next_word(R.chunks[ci].cs_prefix, 0);
+          if (w < chunk_words[ci]) { at.chunk = ci; at.word = w; have = true; }
+        }
+      }
+      if (have) {
+        gk_engine::ResChunk& c = R.chunks[at.chunk];
+        gk_table* t = c.table;
+        const uint32_t w0 = at.word, w1 = viol_page_end(c.cs_prefix, w0, max_objects);
+        const uint32_t rows = std::min<uint32_t>(c.ev->n_constraints, nc);
+        const bool use_base = !reset && c.cs_has_base;
+        page_chunk = at.chunk;
+        // the page's slots are the index's words; every plan group emits its masks of the two sides for them
+        for (uint32_t w = w0; w < w1; w++)
+          for (uint64_t m = c.cs_changed[w]; m; m &= m - 1) slots.push_back(w * 64u + (uint32_t)__builtin_ctzll(m));
+        std::vector<uint32_t> off((size_t)(w1 - w0) + 1);
+        for (uint32_t w = w0; w <= w1; w++) off[w - w0] = (uint32_t)(c.cs_prefix[w] - c.cs_prefix[w0]);
+        const std::vector<uint64_t> extra(c.cs_changed.begin() + w0, c.cs_changed.begin() + w1);
+        h->viol.assign(slots.size() * (size_t)mw, 0); h->err.assign(slots.size() * (size_t)mw, 0);
+        h->was_viol.assign(slots.size() * (size_t)mw, 0); h->was_err.assign(slots.size() * (size_t)mw, 0);
+        each_group(e, t, [&](const GroupAt& g) {
+          if (g.nc == 0) return;
+          std::vector<uint32_t> rev;
+          std::vector<uint64_t> now, was;
+          float m = 0;
+          dev_delta_entries(g.side.dev, g.nc, t->n_reviews, c.shown, c.shown_gen, use_base, w0, w1, off, c.cs_merged ? &extra : nullptr, &rev, &now, &was, &m);
+          device_ms += m;
+          if (rev != slots) throw std::runtime_error("gk_resident_changes: the page's entries do not add up to the chunk's index");
+          if (!viol_scatter(slots, mw, rev, now, g.nc, g.row0, &h->viol) || !viol_scatter(slots, mw, rev, was, g.nc, g.row0, &h->was_viol))
+            throw std::runtime_error("gk_resident_changes: a plan group's entries do not fit the page");
+        });
+        // the pairs no device bitmap carries: autoreject, host-completed violations -- now, and as the baseline kept them
+        delta_pairs_or(c.cs_now_err, slots, mw, rows, &h->err);
+        delta_pairs_or(c.cs_now_hviol, slots, mw, rows, &h->viol);
+        if (use_base) {
+          delta_pairs_or(c.cs_base_err, slots, mw, rows, &h->was_err);
+          delta_pairs_or(c.cs_base_hviol, slots, mw, rows, &h->was_viol);
+        }
+        for (uint32_t slot : slots) h->entry_flags.push_back((c.shown[slot / 64] >> (slot % 64)) & 1ull ? 0u : GK_CHANGE_GONE);
+        // the next page begins at the next word with entries, in this chunk or a later one
+        ViolCursor nx;
+        nx.gen = R.cs_gen;
+        bool more = false;
+        for (uint32_t ci = at.chunk; ci < R.chunks.size() && !more; ci++) {
+          const uint32_t w = viol_next_word(R.chunks[ci].cs_prefix, ci == at.chunk ? w1 : 0);
+          if (w < chunk_words[ci]) { nx.chunk = ci; nx.word = w; more = true; }
+        }
+        if (more) {
+          next_cursor = viol_cursor_pack(nx);
+          if (!next_cursor) throw std::runtime_error("gk_resident_changes: the position does not fit a cursor");
+        }
+      }
+    }
+    // ---- the page's objects: inventory paths, and with GK_CHANGES_RENDER what gk_resident_review answers for those with a result now
+    const gk_engine::ResChunk* pc = slots.empty() ? nullptr : &R.chunks[page_chunk];
+    {
+      std::string& a = h->path_arena;
+      std::vector<size_t> at;
+      at.reserve(slots.size());
+      for (uint32_t slot : slots) {
+        at.push_back(a.size());
+        append_path_json(R.objs[pc->obj_of_slot[slot]].path, a);
+        a += '\0';
+      }
+      h->paths.reserve(slots.size());
+      for (size_t off : at) h->paths.push_back(a.data() + off);   // (after the last append: the arena no longer moves)
+    }
+    if ((flags & GK_CHANGES_RENDER) && !slots.empty()) {
+      std::vector<size_t> todo;   // entries with a result now
+      for (size_t i = 0; i < slots.size(); i++) {
+        uint64_t any = 0;
+        for (uint32_t k = 0; k < mw; k++) any |= h->viol[i * mw + k] | h->err[i * mw + k];
+        if (any) todo.push_back(i);
+      }
+      std::string err;
+      const int st = resident_render_page(e, *pc, slots, todo, &h->result_text, &err);
+      if (st != GK_OK) return fail(st, err);
+      h->results.assign(slots.size(), nullptr);
+      for (size_t i : todo) h->results[i] = h->result_text[i].c_str();
+    }
+    uint64_t base_bytes = 0;
+    {
+      std::shared_lock<std::shared_mutex> pl(e->plan_rw);
+      if (next_cursor == 0) {
+        // ---- the last page: the baseline becomes the streamed state.  A chunk that has a baseline and no entry keeps its copy (what
+        // it shows is what the baseline shows); afterwards every chunk's index against the NEW baseline is known to be empty.
+        if (e->plan_dirty || e->plan_gen != R.cs_plan_gen) return fail(GK_ERR_INVALID, k_stream_moved);
+        try {
+          for (auto& c : R.chunks) {
+            if (!reset && c.cs_has_base && c.cs_prefix.back() == 0) continue;
+            each_group(e, c.table, [&](const GroupAt& g) { if (g.nc) dev_delta_keep(g.side.dev, g.nc, c.table->n_reviews, c.shown, c.shown_gen); });
+            c.cs_has_base = true;
+            c.cs_base_shown = c.shown;
+            c.cs_base_err = c.cs_now_err; c.cs_base_hviol = c.cs_now_hviol;
+          }
+        } catch (...) {   // (half a baseline is none: the next stream starts over)
+          R.cs_base_gen = 0;
+          for (auto& c : R.chunks) { c.cs_has_base = false; c.cs_prefix.clear(); }
+          throw;
+        }
+        R.cs_base_gen++;
+        R.cs_base_compactions = R.compactions;
+        R.cs_base_ids = changes_group_ids(e);
+        for (auto& c : R.chunks) {
+          std::fill(c.cs_prefix.begin(), c.cs_prefix.end(), 0);
+          std::fill(c.cs_changed.begin(), c.cs_changed.end(), 0);
+          c.cs_merged = e->groups.size() > 1 && c.table->sides.size() > 1;
+          c.cs_base_gen = R.cs_base_gen; c.cs_reset = false;
+        }
+      }
+      for (auto& c : R.chunks) each_group(e, c.table, [&](const GroupAt& g) { base_bytes += dev_delta_bytes(g.side.dev); });
+    }
+    gk_changes_out& p = h->pub;
+    memset(&p, 0, sizeof p);
+    p.n_objects = R.n_live; p.n_constraints = nc; p.n_chunks = (uint32_t)R.chunks.size(); p.mask_words = mw;
+    p.constraint_ids = h->ids.data();
+    p.reset = reset ? 1u : 0u;
+    p.total_entries = total;
+    p.n_entries = (uint32_t)slots.size();
+    p.paths = h->paths.empty() ? nullptr : h->paths.data();
+    p.viol = h->viol.data(); p.err = h->err.data(); p.was_viol = h->was_viol.data(); p.was_err = h->was_err.data();
+    p.entry_flags = h->entry_flags.data();
+    p.results_json = h->results.empty() ? nullptr : h->results.data();
+    p.beyond_limits = beyond;
+    p.next_cursor = next_cursor;
+    p.device_ms = device_ms;
+    p.baseline_bytes = base_bytes;
+    *out = &h.release()->pub;
+    return GK_OK;
+  } catch (const std::exception& ex) { return fail(GK_ERR_DEVICE, ex.what()); }
+}
+
+void gk_changes_free(gk_changes_out* o) { if (o) delete reinterpret_cast<ChangesHolder*>(o); }
 
 // ---- gk_table_violations: every review of a table with at least one result in its most recent evaluation, in pages (table_stream.hpp
 // holds the pure part; the device compacts both bitmaps of all plan groups: dev_tviol_index / dev_tviol_entries)

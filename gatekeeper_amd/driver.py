@@ -906,6 +906,44 @@ class Driver:
             if not cursor:
                 return
 
+    def ResidentChanges(self, max_objects=4096, render=True, restart=False):
+        """gk_resident_changes as a generator over its pages: what differs in ResidentViolations' answer since the last changes stream that
+        was read to its end.  Yields one dict per page -- reset, total_entries, device_ms, baseline_bytes, beyond_limits and entries, a list
+        of (inventory path tuple, {"viol", "err", "was_viol", "was_err": [constraint ids]}, gone, rows of gk_query's JSON or None) in stream
+        order -- and frees each page.  The baseline advances when the last page has been returned: a generator dropped before that leaves
+        it alone.  A put / remove or a policy change while the generator is open makes its next page fail (EngineError, GK_ERR_INVALID)."""
+        lib, cursor = self.engine.lib, 0
+        flags = (L.GK_CHANGES_RENDER if render else 0) | (L.GK_CHANGES_RESTART if restart else 0)
+        while True:
+            out = C.POINTER(L.gk_changes_out)()
+            self.engine._check(lib.gk_resident_changes(self.engine.handle, cursor, int(max_objects), flags, C.byref(out)))
+            try:
+                o = out.contents
+                ids, mw = [int(o.constraint_ids[i]) for i in range(o.n_constraints)], int(o.mask_words)
+                entries = []
+                for i in range(o.n_entries):
+                    sets = {}
+                    for name, arr in (("viol", o.viol), ("err", o.err), ("was_viol", o.was_viol), ("was_err", o.was_err)):
+                        got = []
+                        for w in range(mw):
+                            m = int(arr[i * mw + w])
+                            while m:
+                                low = m & -m
+                                got.append(ids[w * 64 + low.bit_length() - 1])
+                                m ^= low
+                        sets[name] = got
+                    text = o.results_json[i] if render and o.results_json else None
+                    entries.append((tuple(json.loads(o.paths[i].decode())), sets, bool(o.entry_flags[i] & L.GK_CHANGE_GONE),
+                                    json.loads(text.decode()) if text is not None else None))
+                page = {"reset": bool(o.reset), "total_entries": int(o.total_entries), "device_ms": float(o.device_ms), "baseline_bytes": int(o.baseline_bytes),
+                        "beyond_limits": int(o.beyond_limits), "n_chunks": int(o.n_chunks), "constraint_ids": ids, "entries": entries}
+                cursor = int(o.next_cursor)
+            finally:
+                lib.gk_changes_free(out)
+            yield page
+            if not cursor:
+                return
+
     def _verify_result(self, out, paths=None):
         o = out.contents
         try:
@@ -1247,6 +1285,27 @@ class Client:
                     res.append(Result(v["msg"], c, {} if v.get("autoreject") else v.get("details", {}), ea, scoped))
             if res:
                 yield path, res
+
+    def AuditChangesFromCache(self, page=4096):
+        """AuditStreamFromCache for a caller that keeps the previous cycle's results: a generator over gk_resident_changes' pages, each
+        (reset, [(path tuple, appeared [Result], resolved [(constraint kind, name)], gone)]).  `appeared` is everything the entry has now at
+        the audit enforcement point, built as AuditStreamFromCache builds it; `resolved` names the constraints that had a result at the
+        baseline and have none now.  reset: drop what was kept, the stream is the whole state.  Apply the entries in order."""
+        info = self._active(AUDIT_EP)
+        names = {cid: key for key, cid in self.driver._ids.items()}
+        for pg in self.driver.ResidentChanges(page, render=True):
+            out = []
+            for path, sets, gone, rows in pg["entries"]:
+                res = []
+                for v in rows or ():
+                    if v["constraint"] in info:
+                        c, ea, scoped = info[v["constraint"]]
+                        res.append(Result(v["msg"], c, {} if v.get("autoreject") else v.get("details", {}), ea, scoped))
+                now = set(sets["viol"]) | set(sets["err"])
+                resolved = sorted({names[cid] for cid in sets["was_viol"] + sets["was_err"] if cid not in now and cid in info and cid in names})
+                if res or resolved or gone:
+                    out.append((path, res, resolved, gone))
+            yield pg["reset"], out
 
     def AuditViolationMessages(self, timestamp, page=4096, msg_size=256):
         """What an audit run publishes per result: one dict per Result of the resident set in violationMsg's shape (manager.go:1188-1212;

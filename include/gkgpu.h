@@ -409,6 +409,60 @@ typedef struct {
 } gk_violations_out;
 int gk_resident_violations(gk_engine* e, uint64_t cursor, uint32_t max_objects, uint32_t flags, gk_violations_out** out);
 void gk_violations_free(gk_violations_out* o);
+/* What CHANGED in that answer since the caller last took it: a consumer that mirrors the results into constraint status, events or an
+ * export handles entries proportional to the change, not to the set.  (The engine's own host work is proportional to the change per
+ * chunk that nothing touched -- such a chunk keeps its index and its baseline; for a chunk in which a slot died or was hidden it lists
+ * the chunk's autoreject pairs again from the downloaded error bitmap and copies the chunk's bitmap again at the commit.)  Let S(state) be the map {inventory path -> (viol mask, err mask)}
+ * that a complete gk_resident_violations stream returns for a state of the set -- shown objects only, autoreject pairs, host-completed
+ * pairs and objects beyond the device's limits handled exactly as there.  The engine keeps one BASELINE B, the state at which the last
+ * changes stream was handed out completely; a stream begun now, at state N, reports what differs between S(B) and S(N).
+ * An entry is one slot of one chunk: the object's path, viol / err (now) and was_viol / was_err (at the baseline).  A slot has an entry
+ * iff now != was.  A slot that is no longer shown counts as now = 0 (a removed object, a replaced one, one a new process excluder
+ * hides) and carries GK_CHANGE_GONE; a slot of a chunk that did not exist at the baseline counts as was = 0.  A replaced object
+ * therefore yields up to two entries, first its old slot (now = 0), then its new version (was = 0) -- in this order, because the
+ * stream goes chunk by chunk and a new version always lives in a later chunk -- and an object that was flattened again and has results
+ * now always appears, even with equal masks: its messages may differ.  A consumer applies the entries in stream order,
+ * "state[path] := now".  Per chunk and plan group the device compares the bitmaps of the last sweep with a device copy kept at the
+ * baseline (allocated at the first gk_resident_changes: an engine that never calls it pays nothing) and compacts the differing slots
+ * into (slot, mask now, mask then) entries; autoreject pairs and host-completed pairs are compared on the host.
+ * Pages and cursors are gk_resident_violations': whole 64-slot words of one chunk, entries <= max_objects (below 64 counts as 64);
+ * cursor 0 begins a stream and brings the set up to date; a later page evaluates nothing and is refused with GK_ERR_INVALID ("... start
+ * again with cursor 0") when a put or remove, a policy change, a new process excluder or a compaction came between.  The two streams
+ * keep generations of their own and do not invalidate each other.
+ * The baseline advances to the streamed state when the page with next_cursor == 0 is returned, and only then: an abandoned or refused
+ * stream leaves it alone, beginning again returns the same entries plus whatever changed since, and a stream begun right after a
+ * completed one has total_entries == 0.
+ * reset = 1, on every page of a stream, says that no comparable baseline exists -- the first call, GK_CHANGES_RESTART at cursor 0, a
+ * compaction of the set since the baseline, or constraint ids per plan group in bitmap-row order that differ from the baseline's.  A
+ * reset stream is the whole state, exactly gk_resident_violations' entries with was = 0; the consumer drops what it holds.  A policy
+ * recompile that leaves the row layout as it was is NOT a reset: the bitmaps are answers and stay comparable.  A compaction does reset
+ * (the slots move); that costs far less than the re-flatten that causes it.
+ * With GK_CHANGES_RENDER, results_json[i] is byte for byte gk_resident_review's answer for every entry with a result now and NULL for
+ * the others; rendering runs on the host workers (GK_HOST_THREADS). */
+#define GK_CHANGES_RENDER 1u
+#define GK_CHANGES_RESTART 2u
+#define GK_CHANGE_GONE 1u
+typedef struct {
+  uint64_t n_objects;               /* live objects */
+  uint32_t n_constraints, n_chunks, mask_words;   /* mask_words = ceil(n_constraints / 64) */
+  const uint32_t* constraint_ids;   /* [n_constraints], bitmap-row order: bit r of a mask = constraint_ids[r] */
+  uint32_t reset;                   /* 1: no comparable baseline, the stream is the whole state (every page says so) */
+  uint64_t total_entries;           /* entries of the WHOLE stream, on every page */
+  uint32_t n_entries;               /* on this page */
+  const char* const* paths;         /* [n_entries] JSON array of inventory path segments */
+  const uint64_t* viol;             /* [n_entries][mask_words] violated constraints now */
+  const uint64_t* err;              /* [n_entries][mask_words] autoreject now */
+  const uint64_t* was_viol;         /* [n_entries][mask_words] ... at the baseline */
+  const uint64_t* was_err;          /* [n_entries][mask_words] */
+  const uint32_t* entry_flags;      /* [n_entries] GK_CHANGE_GONE: the slot is no longer shown */
+  const char* const* results_json;  /* [n_entries] with GK_CHANGES_RENDER (NULL for an entry without results now); else NULL */
+  uint64_t beyond_limits;           /* as gk_sweep_out */
+  uint64_t next_cursor;             /* 0: this was the last page -- the baseline is now the streamed state */
+  float device_ms;                  /* HIP-event time of this call's kernels */
+  uint64_t baseline_bytes;          /* diagnostic, no part of the contract above: device memory the baseline holds after this call */
+} gk_changes_out;
+int gk_resident_changes(gk_engine* e, uint64_t cursor, uint32_t max_objects, uint32_t flags, gk_changes_out** out);
+void gk_changes_free(gk_changes_out* o);
 /* The same for the list-based audit (gk_table_create / gk_table_create_spool + gk_table_eval): gk_table_violations names every review
  * of the table that has at least one result in the table's most recent collected evaluation -- it evaluates nothing itself, and works
  * behind GK_EVAL_NO_DOWNLOAD and GK_EVAL_DEVICE_ONLY evaluations as well, so an audit never has to bring the bitmaps back.  The device
