@@ -132,6 +132,38 @@ void dev_tviol_entries(const std::vector<TviolSide>& sides, uint32_t n_reviews, 
 // three bitmaps beside the table's address; the device reads its own buffers and does nothing here) / the table (view) is going away
 void dev_tviol_note(const DevTable* t, const EvalOut& o);
 void dev_tviol_forget(const DevTable* t);
+// table changes stream (gk_table_snapshot / gk_table_changes): one list-based audit cycle's answer compared with a kept earlier one.
+// dev_snap_take copies what dev_tviol_index would read -- the bitmaps of all sides, device to device -- into ONE flat layout,
+// viol / err = [rows][pw] with every side's rows at its row0 (rows = the largest row0 + nc, pw = ceil(n_reviews / 64)), plus the OR of
+// the sides' too_big words; the snapshot owns its memory (device pool) and outlives the table.
+// dev_tchg_align lines a snapshot up with a table of `n` reviews: was_viol / was_err = [rows_now][ceil(n / 64)] where bit i of row r is
+// bit then_of[i] of the snapshot's row row_of[r] (then_of[i] / row_of[r] == 0xFFFFFFFF: zero; then_of == nullptr: the identity over the
+// snapshot's own reviews, n = its count), and was_big likewise from the snapshot's too_big words.  A null snapshot aligns to all zero
+// without buffers.  `moved` (reviews whose version differs) and `only` (the reviews the side is about; none: all) are [ceil(n / 64)]
+// words the aligned side keeps with it.  The caller owns the result (dev_tchg_free) and keeps it for the life of a stream.
+// dev_tchg_index: changed[w] = the reviews of word w with (viol ^ was_viol) | (err ^ was_err) != 0 in some row, the was side read under
+// NOT was_big, or that are in `moved` and have a bit now; all under care = below n, in `only`, NOT in any side's too_big.  big[w] = the
+// sides' too_big bits below n, *beyond their number.  Without sides the now side reads as zero (the gone reviews of a snapshot).
+// dev_tchg_entries: the entries of the words [w0, w1) -- reviews ascending, four masks [entries][ceil(rows_now / 64)], bit r = row r of
+// the table now -- of the reviews (changed & ~drop) | extra; drop / extra: [w1 - w0] words or empty.  `off` = the page's slice
+// [w1 - w0 + 1] of the exclusive prefix sum over those words; the call throws when it does not fit the bitmaps.  The now masks of a
+// review with a too_big bit are unspecified.  *ms: HIP-event time of the call's kernels (the CPU stand-in: 0).
+struct DevSnap;
+struct DevAligned;
+DevSnap* dev_snap_take(const std::vector<TviolSide>& sides, uint32_t n_reviews);
+void dev_snap_free(DevSnap* s);
+uint64_t dev_snap_bytes(const DevSnap* s);
+DevAligned* dev_tchg_align(int device, const DevSnap* s, uint32_t n, const std::vector<uint32_t>* then_of, const std::vector<uint32_t>& row_of,
+                           const std::vector<uint64_t>* moved, const std::vector<uint64_t>* only, float* ms);
+void dev_tchg_free(DevAligned* a);
+void dev_tchg_index(const std::vector<TviolSide>& sides, uint32_t n, const DevAligned* a, std::vector<uint32_t>* cnt, std::vector<uint64_t>* changed,
+                    std::vector<uint64_t>* big, uint64_t* beyond, float* ms);
+void dev_tchg_entries(const std::vector<TviolSide>& sides, uint32_t n, const DevAligned* a, const std::vector<uint32_t>& off, uint32_t w0, uint32_t w1,
+                      const std::vector<uint64_t>& drop, const std::vector<uint64_t>& extra, std::vector<uint32_t>* reviews, std::vector<uint64_t>* viol,
+                      std::vector<uint64_t>* err, std::vector<uint64_t>* was_viol, std::vector<uint64_t>* was_err, float* ms);
+// as dev_tviol_note / dev_tviol_forget, for the CPU stand-in of the entries above (the device does nothing here)
+void dev_tchg_note(const DevTable* t, const EvalOut& o);
+void dev_tchg_forget(const DevTable* t);
 // the violation bitmap [nc][n_tiles] of the table's most recent evaluation (device -> host copy)
 void dev_last_viol(const DevTable* t, uint32_t nc, std::vector<uint64_t>* viol);
 // ---- the plan-specialised kernel checked against the bytecode kernel (gk_table_verify).

@@ -35,6 +35,7 @@
 #include "table_stream.hpp"
 #include "viol_stream.hpp"
 #include "delta_stream.hpp"
+#include "table_delta.hpp"
 
 using namespace gk;
 
@@ -486,6 +487,19 @@ struct gk_table {
   bool ts_pending = false;
   std::vector<uint32_t> host_done, ts_dev_off;
   std::vector<uint64_t> ts_prefix;
+  // gk_table_changes: the state of the stream begun by the last call with cursor 0, valid while ts_gen stands (tc.gen) -- per side
+  // (0: the table's reviews, 1: the snapshot's gone ones) what the device lined up (freed when the result buffers move or the table
+  // goes), the index (table_delta.hpp), the host-known reviews and what the device is told of them
+  struct Changes {
+    uint32_t gen = 0, flags = 0;            // (flags: as given at cursor 0)
+    uint64_t snap_serial = 0;               // the snapshot the stream compares with (0: none, a reset stream)
+    DevAligned* aligned[2] = {nullptr, nullptr};
+    uint32_t n[2] = {0, 0};
+    std::vector<uint64_t> prefix[2], drop[2], extra[2], moved;
+    DeltaKnownMap known[2];
+    std::vector<uint32_t> then_of;
+    uint64_t beyond = 0;
+  } tc;
   uint32_t n_reviews = 0;
   uint32_t rpt = GK_RPT_MIN;                // reviews per row group of this table
   uint64_t dict_gen = 0;                    // generation of the dictionary-predicate registry the rows were flattened under
@@ -545,7 +559,11 @@ void table_sides(const gk_engine* e, gk_table* t) {
 
 // a launch is about to write the table's result buffers (or a collecting call to finish them): gk_table_violations' stream generation
 // moves, so that no cursor handed out before is answered from the new bitmaps
-void table_results_move(gk_table* t) { t->ts_gen = viol_next_gen(t->ts_gen); }
+void table_changes_drop(gk_table* t) {
+  for (DevAligned*& a : t->tc.aligned) { dev_tchg_free(a); a = nullptr; }
+  t->tc = gk_table::Changes();
+}
+void table_results_move(gk_table* t) { t->ts_gen = viol_next_gen(t->ts_gen); if (t->tc.gen || t->tc.aligned[0] || t->tc.aligned[1]) table_changes_drop(t); }
 
 // One plan group as seen from one table: the engine's group `grp` (its base plan: grp.dev), the table's side of it (what it evaluates
 // into: side.dev; the plan this table runs it on, once table_plans chose it: side.plan), its number of bitmap rows and its first row
@@ -1748,12 +1766,14 @@ int gk_table_get_stats(const gk_table* t, gk_table_stats* out) {
 void gk_table_free(gk_table* t) {
   if (!t) return;
   for (DevTable* v : t->tviews) dev_table_free(v);
+  table_changes_drop(t);
   for (size_t g = t->sides.size(); g-- > 0;) {   // (views before the table: side 0 last)
     gk_table::Side& s = t->sides[g];
     if (s.vview) { dev_verify_forget(s.vview); dev_table_free(s.vview); }
     dev_plan_free(s.vtwin);
     dev_verify_forget(s.dev);
     dev_tviol_forget(s.dev);
+    dev_tchg_forget(s.dev);
     dev_delta_drop(s.dev);
     dev_table_free(s.dev);
   }
@@ -1807,10 +1827,10 @@ int gk_table_eval(gk_engine* e, gk_table* t, uint32_t flags, gk_eval_out** out) 
       // collected in group order: the primary group's answer is the call's, the rows of every further group are appended below it
       each_group(e, t, [&](const GroupAt& g) {
         EvalOut& o = h->out;
-        if (g.g == 0) { dev_eval_finish(g.side.plan, g.side.dev, opt, &o); dev_tviol_note(g.side.dev, o); h->lds_bytes = o.lds_bytes; return; }
+        if (g.g == 0) { dev_eval_finish(g.side.plan, g.side.dev, opt, &o); dev_tviol_note(g.side.dev, o); dev_tchg_note(g.side.dev, o); h->lds_bytes = o.lds_bytes; return; }
         EvalOut og;
         dev_eval_finish(g.side.plan, g.side.dev, opt, &og);
-        dev_tviol_note(g.side.dev, og);
+        dev_tviol_note(g.side.dev, og); dev_tchg_note(g.side.dev, og);
         const uint32_t row_base = o.n_constraints;
         o.viol.insert(o.viol.end(), og.viol.begin(), og.viol.end());
         o.err.insert(o.err.end(), og.err.begin(), og.err.end());
@@ -3047,7 +3067,7 @@ static int verify_table(gk_engine* e, gk_table* t, uint32_t flags, uint32_t max_
     if (ng > 1) each_group(e, t, [&](const GroupAt& g) { dev_jit_prefetch(g.side.plan, g.side.dev); });   // (the builds compile side by side)
     std::vector<EvalOut> A(ng), B(ng);
     table_results_move(t);
-    each_group(e, t, [&](const GroupAt& g) { dev_verify_eval(g.side.plan, g.side.dev, oa, &A[g.g]); dev_tviol_note(g.side.dev, A[g.g]); });
+    each_group(e, t, [&](const GroupAt& g) { dev_verify_eval(g.side.plan, g.side.dev, oa, &A[g.g]); dev_tviol_note(g.side.dev, A[g.g]); dev_tchg_note(g.side.dev, A[g.g]); });
     each_group(e, t, [&](const GroupAt& g) { dev_verify_eval(g.side.vtwin ? g.side.vtwin : g.side.plan, g.side.vview, ob, &B[g.g]); });
     t->last_nc = (uint32_t)ids.size(); t->last_ids = ids;   // (the table's bitmaps are this evaluation's now, as after gk_table_eval)
     t->ts_pending = false; t->eval_plan_gen = gen;
@@ -3742,6 +3762,35 @@ std::string table_entry_json(gk_engine* e, gk_table* t, const std::vector<uint32
   }
   return out + "]";
 }
+// The entries of a page rendered on the host workers (GK_HOST_THREADS): texts[i] = table_entry_json of entry i, for every entry or, with
+// `todo`, for the listed ones (the others stay empty).  Returns the first error's text (the remaining entries are then not rendered).
+std::string table_render_entries(gk_engine* e, gk_table* t, const std::vector<uint32_t>& ids, const std::vector<uint32_t>& reviews, const std::vector<uint64_t>& viol,
+                                 const std::vector<uint64_t>& err, uint32_t mw, const std::vector<size_t>* todo, std::vector<std::string>* texts) {
+  const size_t n = todo ? todo->size() : reviews.size();
+  texts->assign(reviews.size(), std::string());
+  std::string first_err;
+  if (n == 0) return first_err;
+  size_t n_threads = std::max<size_t>(1, std::min<size_t>(host_cpus(), n));
+  if (const char* ht = getenv("GK_HOST_THREADS")) n_threads = std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, atoi(ht)), n));
+  std::atomic<size_t> next{0};
+  std::mutex err_mu;
+  auto worker = [&](size_t) {   // one entry per task, handed out in page order
+    for (;;) {
+      const size_t k = next.fetch_add(1);
+      if (k >= n) return;
+      const size_t i = todo ? (*todo)[k] : k;
+      try {
+        (*texts)[i] = table_entry_json(e, t, ids, reviews[i], viol.data() + i * mw, err.data() + i * mw);
+      } catch (const std::exception& ex) {
+        std::lock_guard<std::mutex> l(err_mu);
+        if (first_err.empty()) first_err = ex.what()[0] ? ex.what() : "rendering failed";
+        next.store(n);   // (the call fails: the remaining entries are not rendered)
+      }
+    }
+  };
+  HostWorkers::get().run(n_threads, worker);
+  return first_err;
+}
 }  // namespace
 
 int gk_table_violations(gk_engine* e, gk_table* t, uint64_t cursor, uint32_t max_entries, uint32_t flags, gk_table_violations_out** out) {
@@ -3816,27 +3865,7 @@ int gk_table_violations(gk_engine* e, gk_table* t, uint64_t cursor, uint32_t max
     }
     const uint32_t mw = ((uint32_t)h->ids.size() + 63u) / 64u;
     if ((flags & GK_VIOLATIONS_RENDER) && !h->reviews.empty()) {
-      const size_t n = h->reviews.size();
-      h->result_text.resize(n);
-      size_t n_threads = std::max<size_t>(1, std::min<size_t>(host_cpus(), n));
-      if (const char* ht = getenv("GK_HOST_THREADS")) n_threads = std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, atoi(ht)), n));
-      std::atomic<size_t> next{0};
-      std::mutex err_mu;
-      std::string first_err;
-      auto worker = [&](size_t) {   // one entry per task, handed out in page order
-        for (;;) {
-          const size_t i = next.fetch_add(1);
-          if (i >= n) return;
-          try {
-            h->result_text[i] = table_entry_json(e, t, h->ids, h->reviews[i], h->viol.data() + i * mw, h->err.data() + i * mw);
-          } catch (const std::exception& ex) {
-            std::lock_guard<std::mutex> l(err_mu);
-            if (first_err.empty()) first_err = ex.what()[0] ? ex.what() : "rendering failed";
-            next.store(n);   // (the call fails: the remaining entries are not rendered)
-          }
-        }
-      };
-      HostWorkers::get().run(n_threads, worker);
+      const std::string first_err = table_render_entries(e, t, h->ids, h->reviews, h->viol, h->err, mw, nullptr, &h->result_text);
       if (!first_err.empty()) return fail(GK_ERR_REGO, first_err);
       for (const std::string& r : h->result_text) h->results.push_back(r.c_str());
     }
@@ -3858,6 +3887,315 @@ int gk_table_violations(gk_engine* e, gk_table* t, uint64_t cursor, uint32_t max
 }
 
 void gk_table_violations_free(gk_table_violations_out* o) { if (o) delete reinterpret_cast<TableViolationsHolder*>(o); }
+
+// ---- gk_table_snapshot / gk_table_changes: one list-based cycle's answer against a kept earlier one (table_delta.hpp holds the pure
+// part; the device lines the snapshot up with the table and compacts the difference: dev_snap_take / dev_tchg_align / _index / _entries)
+struct gk_snapshot {
+  gk_engine* eng = nullptr;
+  uint64_t serial = 0;                    // unique per snapshot of the process: what a stream remembers of its `then`
+  uint32_t n_reviews = 0;
+  std::vector<uint32_t> ids;              // constraint id per bitmap row
+  DevSnap* dev = nullptr;
+  TablePairs host_viol, host_err;         // what the host evaluation of the kept evaluation added
+  std::vector<uint32_t> host_done;        // the reviews it answered, ascending
+  uint64_t beyond = 0;
+  std::string key_bytes;                  // the reviews' keys one after the other ...
+  std::vector<std::pair<uint64_t, uint32_t>> key_span;   // ... (offset, length) per review
+  std::vector<uint32_t> order;            // the reviews in key order (table_key_order)
+  std::vector<uint64_t> versions;
+  bool has_versions = false;
+  std::string_view key(size_t i) const { return std::string_view(key_bytes.data() + key_span[i].first, key_span[i].second); }
+  ~gk_snapshot() { dev_snap_free(dev); }
+};
+
+namespace {
+struct TableChangesHolder {
+  gk_table_changes_out pub;   // first member
+  std::vector<uint32_t> ids, reviews, was_reviews, flags;
+  std::vector<uint64_t> viol, err, was_viol, was_err;
+  std::vector<std::string> key_text, result_text;
+  std::vector<const char*> keys, results;
+};
+std::atomic<uint64_t> g_snapshot_serial{0};
+
+// why the answer of the table's most recent evaluation cannot be read (empty: it can) -- gk_table_violations' refusals; plan_rw held
+std::string table_answer_refusal(const gk_engine* e, const gk_table* t, const char* who, bool later_page) {
+  const std::string w = std::string(who) + ": ";
+  if (!t->sides.empty() && !t->sides[0].shard.shard_reviews.empty())
+    return w + "the table is set up as a shard (gk_table_sweep_sharded), its bitmaps live in the exchange buffer: use a table of its own";
+  if (t->ts_pending) return w + "launches of the table are still to be collected (gk_table_eval without GK_EVAL_ASYNC)";
+  if (t->ts_gen == 0 || t->eval_plan_gen == 0) return w + "evaluate the table first (gk_table_eval)";
+  if (e->plan_dirty || e->plan_gen != t->eval_plan_gen)
+    return later_page ? std::string(k_table_stream_moved) : w + "the policies changed since the table was evaluated: evaluate it again (gk_table_eval)";
+  return std::string();
+}
+// the table's sides as the device entries take them; false: the table was not evaluated under the plan groups there are now
+bool table_tviol_sides(const gk_engine* e, gk_table* t, uint32_t nc, std::vector<TviolSide>* sides) {
+  uint32_t rows = 0;
+  each_group(e, t, [&](const GroupAt& g) { sides->push_back(TviolSide{g.side.dev, g.nc, g.row0}); rows = g.row0 + g.nc; });
+  return rows == nc;
+}
+void append_key_json(std::string_view key, std::string& out) {
+  out += '[';
+  size_t at = 0;
+  for (int part = 0; part < 5; part++) {
+    size_t end = part == 4 ? key.size() : key.find('\0', at);
+    if (end == std::string_view::npos) end = key.size();
+    if (part) out += ',';
+    json_escape(std::string(key.substr(std::min(at, key.size()), end - std::min(at, key.size()))), out);
+    at = std::min(end + 1, key.size() + 1);
+  }
+  out += ']';
+}
+std::vector<uint32_t> narrow_slice(const std::vector<uint64_t>& prefix, uint32_t w0, uint32_t w1) {
+  std::vector<uint32_t> off((size_t)(w1 - w0) + 1);
+  for (uint32_t w = w0; w <= w1; w++) off[w - w0] = (uint32_t)(prefix[w] - prefix[w0]);
+  return off;
+}
+std::vector<uint64_t> word_slice(const std::vector<uint64_t>& words, uint32_t w0, uint32_t w1) {
+  return words.empty() ? std::vector<uint64_t>() : std::vector<uint64_t>(words.begin() + w0, words.begin() + w1);
+}
+}  // namespace
+
+int gk_table_snapshot(gk_engine* e, gk_table* t, const uint64_t* versions, gk_snapshot** out) {
+  if (!e || !t || !out) return fail(GK_ERR_INVALID, "NULL argument");
+  try {
+    if (const char* why = table_stale(e, t)) return fail(GK_ERR_INVALID, why);
+    std::unique_ptr<gk_snapshot> s(new gk_snapshot());
+    s->eng = e; s->n_reviews = t->n_reviews;
+    {
+      std::shared_lock<std::shared_mutex> l(e->plan_rw);
+      const std::string why = table_answer_refusal(e, t, "gk_table_snapshot", false);
+      if (!why.empty()) return fail(GK_ERR_INVALID, why);
+      s->ids = t->last_ids;
+      std::vector<TviolSide> sides;
+      if (!table_tviol_sides(e, t, (uint32_t)s->ids.size(), &sides)) return fail(GK_ERR_INVALID, "gk_table_snapshot: evaluate the table first (gk_table_eval)");
+      {
+        std::lock_guard<std::mutex> hl(t->host_mu);
+        if (t->host_gen == t->ts_gen && t->host_ids == s->ids) { s->host_viol = t->host_viol; s->host_err = t->host_err; s->host_done = t->host_done; }
+      }
+      std::sort(s->host_done.begin(), s->host_done.end());
+      s->dev = dev_snap_take(sides, t->n_reviews);
+      std::vector<uint32_t> cnt;
+      uint64_t dev_beyond = 0;
+      float ms = 0;
+      dev_tviol_index(sides, t->n_reviews, &cnt, nullptr, &dev_beyond, &ms);
+      s->beyond = dev_beyond > s->host_done.size() ? dev_beyond - s->host_done.size() : 0;
+    }
+    table_key_order(t);
+    s->order = t->order;
+    s->key_span.resize(t->n_reviews);
+    size_t bytes = 0;
+    for (size_t i = 0; i < t->n_reviews; i++) bytes += t->obj_key(i).size();
+    s->key_bytes.reserve(bytes);
+    for (size_t i = 0; i < t->n_reviews; i++) {
+      const std::string_view k = t->obj_key(i);
+      s->key_span[i] = {s->key_bytes.size(), (uint32_t)k.size()};
+      s->key_bytes.append(k.data(), k.size());
+    }
+    if (versions) { s->versions.assign(versions, versions + t->n_reviews); s->has_versions = true; }
+    s->serial = ++g_snapshot_serial;
+    *out = s.release();
+    return GK_OK;
+  } catch (const std::exception& ex) { return fail(GK_ERR_DEVICE, ex.what()); }
+}
+
+void gk_snapshot_free(gk_snapshot* s) { delete s; }
+
+int gk_snapshot_info(const gk_snapshot* s, struct gk_snapshot_info* out) {
+  if (!s || !out) return fail(GK_ERR_INVALID, "NULL argument");
+  memset(out, 0, sizeof *out);
+  out->n_reviews = s->n_reviews; out->n_constraints = (uint32_t)s->ids.size();
+  out->constraint_ids = s->ids.data();
+  out->device_bytes = dev_snap_bytes(s->dev);
+  out->host_bytes = s->key_bytes.size() + s->key_span.size() * sizeof(s->key_span[0]) + (s->order.size() + s->ids.size() + s->host_done.size()) * 4u + s->versions.size() * 8u +
+                    (s->host_viol.size() + s->host_err.size()) * 8u;
+  out->beyond_limits = s->beyond;
+  return GK_OK;
+}
+
+int gk_table_changes(gk_engine* e, gk_table* t, const gk_snapshot* then, const uint64_t* versions, uint64_t cursor, uint32_t max_entries, uint32_t flags,
+                     gk_table_changes_out** out) {
+  if (!e || !t || !out) return fail(GK_ERR_INVALID, "NULL argument");
+  if (cursor == 0 && (flags & GK_CHANGES_RENDER) && t->docs.size() != t->n_reviews && t->texts.size() != t->n_reviews)
+    return fail(GK_ERR_INVALID, "gk_table_changes: GK_CHANGES_RENDER needs a table created with GK_TABLE_KEEP_DOCS / GK_TABLE_KEEP_TEXT");
+  if (then && then->eng != e) return fail(GK_ERR_INVALID, "gk_table_changes: the snapshot belongs to another engine");
+  try {
+    if (const char* why = table_stale(e, t)) return fail(GK_ERR_INVALID, cursor ? k_table_stream_moved : why);
+    std::unique_ptr<TableChangesHolder> h(new TableChangesHolder());
+    float align_ms = 0, index_ms = 0, emit_ms = 0;
+    uint32_t stream_flags = 0;
+    uint64_t next_cursor = 0, total = 0, beyond = 0;
+    uint32_t page_side = 0;
+    gk_table::Changes& C = t->tc;
+    {
+      std::shared_lock<std::shared_mutex> l(e->plan_rw);
+      const std::string why = table_answer_refusal(e, t, "gk_table_changes", cursor != 0);
+      if (!why.empty()) return fail(GK_ERR_INVALID, why);
+      h->ids = t->last_ids;
+      const uint32_t nc = (uint32_t)h->ids.size(), mw = (nc + 63u) / 64u, n_now = t->n_reviews, n_then = then ? then->n_reviews : 0u;
+      const uint32_t words[2] = {(n_now + 63u) / 64u, (n_then + 63u) / 64u};
+      std::vector<TviolSide> sides;
+      if (!table_tviol_sides(e, t, nc, &sides)) return fail(GK_ERR_INVALID, "gk_table_changes: evaluate the table first (gk_table_eval)");
+      uint32_t side = 0, word = 0;
+      if (cursor == 0) {
+        table_changes_drop(t);
+        C.snap_serial = then ? then->serial : 0;
+        C.flags = flags;
+        C.n[0] = n_now; C.n[1] = n_then;
+        // what the host evaluation of THIS evaluation added (another evaluation's, another policy set's: none of it)
+        TablePairs hv, he;
+        std::vector<uint32_t> done;
+        {
+          std::lock_guard<std::mutex> hl(t->host_mu);
+          if (t->host_gen == t->ts_gen && t->host_ids == h->ids) { hv = t->host_viol; he = t->host_err; done = t->host_done; }
+        }
+        std::sort(done.begin(), done.end());
+        std::vector<uint32_t> row_of(nc, DELTA_NONE), now_row_of, now_of;
+        std::vector<uint64_t> unmatched;
+        C.then_of.assign(n_now, DELTA_NONE);
+        if (then) {
+          delta_row_map(h->ids, then->ids, &row_of, &now_row_of);
+          table_key_order(t);
+          delta_join(t->order, [&](uint32_t i) { return t->obj_key(i); }, then->order, [&](uint32_t i) { return then->key(i); }, &C.then_of, &now_of, &unmatched);
+          if (versions && then->has_versions) {
+            C.moved.assign(words[0], 0);
+            for (uint32_t r = 0; r < n_now; r++)
+              if (C.then_of[r] != DELTA_NONE && then->versions[C.then_of[r]] != versions[r]) C.moved[r / 64u] |= 1ull << (r % 64u);
+          }
+          delta_known_build(done, hv, he, n_now, nc, then->host_done, then->host_viol, then->host_err, now_of, now_row_of, &C.known[0], &C.known[1]);
+        } else {
+          delta_known_build(done, hv, he, n_now, nc, {}, {}, {}, now_of, now_row_of, &C.known[0], &C.known[1]);
+          for (auto& kv : C.known[0]) kv.second.was = true;   // (nothing then: zero)
+        }
+        float ms = 0;
+        // side 0: the table's reviews against what the snapshot holds of them
+        C.aligned[0] = dev_tchg_align(e->opts.device, then ? then->dev : nullptr, n_now, then ? &C.then_of : nullptr, row_of, C.moved.empty() ? nullptr : &C.moved, nullptr, &ms);
+        align_ms += ms;
+        std::vector<uint32_t> cnt;
+        std::vector<uint64_t> changed, big, entries;
+        uint64_t dev_beyond = 0;
+        dev_tchg_index(sides, n_now, C.aligned[0], &cnt, &changed, &big, &dev_beyond, &ms);
+        index_ms += ms;
+        if (changed.size() != words[0] || big.size() != words[0]) throw std::runtime_error("dev_tchg_index: wrong size");
+        C.beyond = dev_beyond > done.size() ? dev_beyond - done.size() : 0;   // (every host-answered review had its too_big bit set)
+        if (!C.known[0].empty()) {
+          C.drop[0] = delta_known_words(C.known[0], words[0]);
+          for (uint32_t w = 0; w < words[0]; w++) {   // the device's masks of the sides the host does not know: word by word, they are few
+            if (!C.drop[0][w]) continue;
+            std::vector<uint32_t> rev;
+            std::vector<uint64_t> v, er, wv, we;
+            dev_tchg_entries(sides, n_now, C.aligned[0], {0u, (uint32_t)__builtin_popcountll(changed[w] | C.drop[0][w])}, w, w + 1, {}, {C.drop[0][w]}, &rev, &v, &er, &wv, &we, &ms);
+            emit_ms += ms;
+            if (!delta_known_fill(&C.known[0], rev, mw, v, er, wv, we)) throw std::runtime_error("gk_table_changes: the device's entries do not fit the host-known reviews");
+          }
+          std::vector<uint64_t> unanswered = big;
+          for (uint32_t r : done) if (r / 64u < words[0]) unanswered[r / 64u] &= ~(1ull << (r % 64u));
+          C.extra[0] = delta_known_decide(C.known[0], words[0], C.moved, unanswered);
+        }
+        if (!delta_prefix(changed, C.drop[0], C.extra[0], &entries, &C.prefix[0])) throw std::runtime_error("gk_table_changes: the index does not fit the host-known reviews");
+        // side 1: the snapshot's reviews nothing in the table continues
+        C.prefix[1].assign((size_t)words[1] + 1, 0);
+        if (then && std::any_of(unmatched.begin(), unmatched.end(), [](uint64_t x) { return x != 0; })) {
+          C.aligned[1] = dev_tchg_align(e->opts.device, then->dev, n_then, nullptr, row_of, nullptr, &unmatched, &ms);
+          align_ms += ms;
+          dev_tchg_index({}, n_then, C.aligned[1], &cnt, &changed, &big, &dev_beyond, &ms);
+          index_ms += ms;
+          if (changed.size() != words[1]) throw std::runtime_error("dev_tchg_index: wrong size");
+          if (!C.known[1].empty()) {
+            C.drop[1] = delta_known_words(C.known[1], words[1]);
+            C.extra[1] = delta_known_decide(C.known[1], words[1], {}, {});
+          }
+          if (!delta_prefix(changed, C.drop[1], C.extra[1], &entries, &C.prefix[1])) throw std::runtime_error("gk_table_changes: the index does not fit the host-known reviews");
+        }
+        if (!delta_next(C.prefix, &side, &word)) side = 2;
+        C.gen = t->ts_gen;   // (set last: a stream whose set-up threw answers no later page)
+      } else {
+        if (C.gen == 0 || C.gen != t->ts_gen || C.prefix[0].size() != (size_t)words[0] + 1) return fail(GK_ERR_INVALID, k_table_stream_moved);
+        if (C.snap_serial != (then ? then->serial : 0) || C.n[1] != n_then)
+          return fail(GK_ERR_INVALID, "gk_table_changes: a later page must name the snapshot the stream began with");
+        if (C.prefix[1].size() != (size_t)words[1] + 1 || !delta_cursor_check(cursor, C.gen, words, &side, &word)) return fail(GK_ERR_INVALID, k_table_stream_moved);
+        uint32_t s2 = side, w2 = word;
+        if (!delta_next(C.prefix, &s2, &w2) || s2 != side || w2 != word) return fail(GK_ERR_INVALID, k_table_stream_moved);   // (no page begins at a word without entries)
+      }
+      stream_flags = C.flags;
+      beyond = C.beyond;
+      total = C.prefix[0].back() + C.prefix[1].back();
+      if (side < 2u) {
+        page_side = side;
+        const uint32_t w0 = word, w1 = viol_page_end(C.prefix[side], w0, max_entries);
+        if (C.prefix[side][w1] - C.prefix[side][w0] > 0xFFFFFFFFull) throw std::runtime_error("gk_table_changes: the page does not fit");
+        std::vector<uint32_t> rev;
+        float ms = 0;
+        dev_tchg_entries(side == 0 ? sides : std::vector<TviolSide>(), C.n[side], C.aligned[side], narrow_slice(C.prefix[side], w0, w1), w0, w1, word_slice(C.drop[side], w0, w1),
+                         word_slice(C.extra[side], w0, w1), &rev, &h->viol, &h->err, &h->was_viol, &h->was_err, &ms);
+        emit_ms += ms;
+        if (!delta_merge_page(C.known[side], rev, mw, C.n[side], w0, w1, &h->viol, &h->err, &h->was_viol, &h->was_err))
+          throw std::runtime_error("gk_table_changes: the device's entries do not fit the page");
+        if (rev.size() != C.prefix[side][w1] - C.prefix[side][w0]) throw std::runtime_error("gk_table_changes: the page's entries do not add up to the stream's index");
+        const size_t n = rev.size();
+        h->key_text.resize(n); h->flags.assign(n, 0);
+        if (side == 0) {
+          h->reviews = rev;
+          h->was_reviews.resize(n);
+          for (size_t i = 0; i < n; i++) {
+            const uint32_t r = rev[i], p = C.then_of[r];
+            h->was_reviews[i] = p;
+            if (p == DELTA_NONE) h->flags[i] |= GK_CHANGE_NEW;
+            else if (!C.moved.empty() && ((C.moved[r / 64u] >> (r % 64u)) & 1ull)) h->flags[i] |= GK_CHANGE_VERSION;
+            append_key_json(t->obj_key(r), h->key_text[i]);
+          }
+        } else {
+          h->was_reviews = rev;
+          h->reviews.assign(n, DELTA_NONE);
+          for (size_t i = 0; i < n; i++) { h->flags[i] = GK_CHANGE_GONE; append_key_json(then->key(rev[i]), h->key_text[i]); }
+        }
+        uint32_t s2 = side, w2 = w1;
+        if (delta_next(C.prefix, &s2, &w2)) {
+          next_cursor = delta_cursor_pack(C.gen, s2, w2);
+          if (!next_cursor) throw std::runtime_error("gk_table_changes: the position does not fit a cursor");
+        }
+      }
+    }
+    const uint32_t mw = ((uint32_t)h->ids.size() + 63u) / 64u;
+    for (const std::string& k : h->key_text) h->keys.push_back(k.c_str());
+    if ((stream_flags & GK_CHANGES_RENDER) && page_side == 0 && !h->reviews.empty()) {
+      const size_t n = h->reviews.size();
+      std::vector<size_t> todo;   // the entries with a result now
+      for (size_t i = 0; i < n; i++) {
+        bool any = false;
+        for (uint32_t k = 0; k < mw; k++) any = any || h->viol[i * mw + k] || h->err[i * mw + k];
+        if (any) todo.push_back(i);
+      }
+      const std::string first_err = table_render_entries(e, t, h->ids, h->reviews, h->viol, h->err, mw, &todo, &h->result_text);
+      if (!first_err.empty()) return fail(GK_ERR_REGO, first_err);
+      h->results.assign(n, nullptr);
+      for (size_t i : todo) h->results[i] = h->result_text[i].c_str();
+    } else if ((stream_flags & GK_CHANGES_RENDER) && !h->was_reviews.empty()) h->results.assign(h->was_reviews.size(), nullptr);
+    gk_table_changes_out& p = h->pub;
+    memset(&p, 0, sizeof p);
+    p.n_reviews = t->n_reviews; p.n_then = then ? then->n_reviews : 0u;
+    p.n_constraints = (uint32_t)h->ids.size(); p.mask_words = mw;
+    p.constraint_ids = h->ids.data();
+    p.reset = then ? 0u : 1u;
+    p.total_entries = total;
+    p.n_entries = (uint32_t)h->flags.size();
+    p.reviews = h->reviews.data(); p.was_reviews = h->was_reviews.data();
+    p.keys = h->keys.data();
+    p.viol = h->viol.data(); p.err = h->err.data(); p.was_viol = h->was_viol.data(); p.was_err = h->was_err.data();
+    p.entry_flags = h->flags.data();
+    p.results_json = h->results.empty() ? nullptr : h->results.data();
+    p.beyond_limits = beyond;
+    p.was_beyond_limits = then ? then->beyond : 0u;
+    p.next_cursor = next_cursor;
+    p.device_ms = align_ms + index_ms + emit_ms;
+    p.align_ms = align_ms; p.index_ms = index_ms; p.emit_ms = emit_ms;
+    *out = &h.release()->pub;
+    return GK_OK;
+  } catch (const std::exception& ex) { return fail(GK_ERR_DEVICE, ex.what()); }
+}
+
+void gk_table_changes_free(gk_table_changes_out* o) { if (o) delete reinterpret_cast<TableChangesHolder*>(o); }
 
 // Driver.Query's `constraints` as a sorted id list; GK_ERR_NOT_FOUND for an id that is not loaded
 static int wanted_ids(gk_engine* e, const uint32_t* ids, size_t n, std::vector<uint32_t>* out) {

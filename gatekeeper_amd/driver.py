@@ -437,6 +437,81 @@ class Table:
                     sets.append(got)
                 yield (int(r), sets[0], sets[1], pg["rows"][i]) if render else (int(r), sets[0], sets[1])
 
+    def snapshot(self, versions=None):
+        """Keep the answer of the most recent collected eval() (gk_table_snapshot): what a later table's change_pages() compares with.
+        versions: one opaque 64-bit value per review (e.g. derived from metadata.resourceVersion), or None.  The table may be freed
+        afterwards; free the Snapshot when no stream needs it any more."""
+        v = None
+        if versions is not None:
+            if len(versions) != self.n:
+                raise ValueError("versions: one value per review")
+            v = (C.c_uint64 * max(1, self.n))(*[int(x) & 0xFFFFFFFFFFFFFFFF for x in versions])
+        h = C.c_void_p()
+        self.engine._check(self.engine.lib.gk_table_snapshot(self.engine.handle, self.handle, v, C.byref(h)))
+        return Snapshot(self.engine, h)
+
+    def change_pages(self, snapshot, page=4096, render=False, versions=None):
+        """gk_table_changes page by page: what differs between `snapshot` (None: nothing, the stream is the whole state) and the most
+        recent collected eval() of this table.  Yields dicts with `ids` (constraint id of every mask bit, this table's), `reset`,
+        `reviews` / `was_reviews` ([n], 0xFFFFFFFF: gone / new), `keys` (per entry the (group, version, kind, namespace, name) tuple),
+        `viol` / `err` / `was_viol` / `was_err` ([n][mask_words] numpy), `flags` ([n] GK_CHANGE_*), `rows` (with `render`: gk_query's
+        rows for an entry with results now, else None), `total_entries`, `beyond_limits`, `was_beyond_limits`, `device_ms`,
+        `next_cursor`.  Frees each page."""
+        lib, cursor = self.engine.lib, 0
+        v = None
+        if versions is not None:
+            if len(versions) != self.n:
+                raise ValueError("versions: one value per review")
+            v = (C.c_uint64 * max(1, self.n))(*[int(x) & 0xFFFFFFFFFFFFFFFF for x in versions])
+        then = snapshot.handle if snapshot is not None else None
+        if snapshot is not None and not then:
+            raise ValueError("the snapshot was freed")
+
+        def masks(ptr, n, mw):
+            return np.ctypeslib.as_array(ptr, (n * mw,)).reshape(n, mw).copy() if n * mw else np.zeros((n, mw), np.uint64)
+        while True:
+            out = C.POINTER(L.gk_table_changes_out)()
+            self.engine._check(lib.gk_table_changes(self.engine.handle, self.handle, then, v, cursor, int(page), L.GK_CHANGES_RENDER if render else 0, C.byref(out)))
+            try:
+                o = out.contents
+                n, mw = int(o.n_entries), int(o.mask_words)
+                pg = {"ids": [int(o.constraint_ids[i]) for i in range(o.n_constraints)], "n_reviews": int(o.n_reviews), "n_then": int(o.n_then),
+                      "mask_words": mw, "reset": int(o.reset),
+                      "reviews": np.ctypeslib.as_array(o.reviews, (n,)).copy() if n else np.zeros(0, np.uint32),
+                      "was_reviews": np.ctypeslib.as_array(o.was_reviews, (n,)).copy() if n else np.zeros(0, np.uint32),
+                      "keys": [tuple(json.loads(o.keys[i].decode())) for i in range(n)],
+                      "viol": masks(o.viol, n, mw), "err": masks(o.err, n, mw), "was_viol": masks(o.was_viol, n, mw), "was_err": masks(o.was_err, n, mw),
+                      "flags": [int(o.entry_flags[i]) for i in range(n)],
+                      "rows": [json.loads(o.results_json[i].decode()) if o.results_json[i] else None for i in range(n)] if render and n and o.results_json else [None] * n,
+                      "total_entries": int(o.total_entries), "beyond_limits": int(o.beyond_limits), "was_beyond_limits": int(o.was_beyond_limits),
+                      "device_ms": float(o.device_ms), "next_cursor": int(o.next_cursor)}
+                cursor = pg["next_cursor"]
+            finally:
+                lib.gk_table_changes_free(out)
+            yield pg
+            if not cursor:
+                return
+
+    def changes(self, snapshot, page=4096, render=False, versions=None):
+        """change_pages() entry by entry: yields (key tuple, {"viol", "err", "was_viol", "was_err": [constraint ids]}, flags, rows,
+        review, was_review) in stream order -- apply them in this order, state[key] := now.  self.beyond_limits /
+        self.was_beyond_limits / self.changes_reset are set from the pages."""
+        for pg in self.change_pages(snapshot, page, render, versions):
+            self.beyond_limits, self.was_beyond_limits, self.changes_reset = pg["beyond_limits"], pg["was_beyond_limits"], pg["reset"]
+            ids = pg["ids"]
+            for i, key in enumerate(pg["keys"]):
+                sets = {}
+                for name in ("viol", "err", "was_viol", "was_err"):
+                    got = []
+                    for w in range(pg["mask_words"]):
+                        m = int(pg[name][i, w])
+                        while m:
+                            low = m & -m
+                            got.append(ids[w * 64 + low.bit_length() - 1])
+                            m ^= low
+                    sets[name] = got
+                yield key, sets, pg["flags"][i], pg["rows"][i], int(pg["reviews"][i]), int(pg["was_reviews"][i])
+
     def stats(self):
         """host-side cost of building the table (gk_table_get_stats) as a dict"""
         st = L.gk_table_stats()
@@ -456,6 +531,30 @@ class Table:
     def free(self):
         if self.handle:
             self.engine.lib.gk_table_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Snapshot:
+    """One audit cycle's answer, kept (gk_snapshot): Table.snapshot() makes it, Table.change_pages() of a later table reads it."""
+
+    def __init__(self, engine, handle):
+        self.engine, self.handle = engine, handle
+
+    def info(self):
+        st = L.gk_snapshot_info()
+        self.engine._check(self.engine.lib.gk_snapshot_info(self.handle, C.byref(st)))
+        return {"n_reviews": int(st.n_reviews), "n_constraints": int(st.n_constraints), "constraint_ids": [int(st.constraint_ids[i]) for i in range(st.n_constraints)],
+                "device_bytes": int(st.device_bytes), "host_bytes": int(st.host_bytes), "beyond_limits": int(st.beyond_limits)}
+
+    def free(self):
+        if self.handle:
+            self.engine.lib.gk_snapshot_free(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -1143,6 +1242,71 @@ class ReviewFailure(ClientError):
         self.cause = cause
 
 
+class AuditCycles:
+    """Consecutive list-based audit cycles of one Client (Client.AuditCycles).  run() is one cycle: one table (resident, process "audit"),
+    one downloading evaluation, gk_table_changes against the previous cycle's snapshot.  The new snapshot replaces the old one only when
+    run()'s generator has been read to its end; close() frees it."""
+
+    def __init__(self, client, page=4096):
+        self.client, self.page, self.snapshot = client, page, None
+
+    def run(self, objs, namespaces=None, versions=None):
+        """Yields (key tuple (group, version, kind, namespace, name), appeared [Result], resolved [(constraint kind, name)], flags) per
+        changed object, built as AuditChangesFromCache builds them: `appeared` is everything the object has now at the audit enforcement
+        point, `resolved` names the constraints that had a result in the previous cycle and have none now; flags: GK_CHANGE_*.  Apply
+        them in order.  An object ReviewBatch fails closed on comes out as (index into objs, ReviewFailure), as in AuditStream.  The
+        first cycle (and the first after close()) is the whole state, every entry GK_CHANGE_NEW."""
+        cl = self.client
+        info = cl._active(AUDIT_EP)
+        names = {cid: key for key, cid in cl.driver._ids.items()}
+        rins, idx = [], []
+        for i, o in enumerate(objs):
+            r = to_review_in(o, namespaces[i] if namespaces else None)
+            if r is not None:
+                rins.append(r)
+                idx.append(i)
+        vers = [versions[i] for i in idx] if versions is not None else None
+        if not rins and self.snapshot is None:
+            return
+        table = cl.driver.engine.create_table(rins, resident=True, process="audit")
+        new = None
+        try:
+            ev = table.eval()
+            for k, st in enumerate(table.statuses):
+                if st not in (L.GK_OK, L.GK_REVIEW_EXCLUDED):
+                    yield idx[k], ReviewFailure(idx[k], "review %d rejected by HandleReview" % idx[k])
+            for k in ev.too_big_reviews():
+                yield idx[k], ReviewFailure(idx[k], str(LimitError("review %d" % idx[k])), LimitError("review %d" % idx[k]))
+            del ev
+            new = table.snapshot(vers)
+            for key, sets, flags, rows, _r, _p in table.changes(self.snapshot, self.page, render=True, versions=vers):
+                res = []
+                for v in sorted((v for v in rows or () if v.get("autoreject")), key=lambda v: v["constraint"]):
+                    if v["constraint"] in info:
+                        c, ea, scoped = info[v["constraint"]]
+                        res.append(Result(v["msg"], c, {}, ea, scoped))
+                for v in sorted((v for v in rows or () if not v.get("autoreject")), key=lambda v: v["constraint"]):
+                    if v["constraint"] in info:
+                        c, ea, scoped = info[v["constraint"]]
+                        res.append(Result(v["msg"], c, v.get("details", {}), ea, scoped))
+                now = set(sets["viol"]) | set(sets["err"])
+                resolved = sorted({names[cid] for cid in sets["was_viol"] + sets["was_err"] if cid not in now and cid in info and cid in names})
+                if res or resolved or flags & L.GK_CHANGE_GONE:
+                    yield key, res, resolved, flags
+            old, self.snapshot, new = self.snapshot, new, None
+            if old is not None:
+                old.free()
+        finally:
+            if new is not None:
+                new.free()
+            table.free()
+
+    def close(self):
+        if self.snapshot is not None:
+            self.snapshot.free()
+            self.snapshot = None
+
+
 class AuditReport(dict):
     """AuditAggregate's answer: {(kind, apiVersion, name): {"total", "total_pairs", "violations"}} plus
     .totals_per_action ({enforcement action: results}, manager.go:904) and .errors ([ReviewFailure])."""
@@ -1396,6 +1560,11 @@ class Client:
                     res.append(Result(v["msg"], c, v.get("details", {}), ea, scoped))
             if res:
                 yield i, res
+
+    def AuditCycles(self, page=4096):
+        """The list-based audit for a caller that keeps the previous cycle's results: an AuditCycles whose run(objs) does one cycle and
+        yields only what changed since the cycle before (gk_table_changes against that cycle's snapshot)."""
+        return AuditCycles(self, page)
 
     def AuditMessages(self, objs, timestamp, namespaces=None, page=4096, msg_size=256):
         """AuditViolationMessages for the list-based audit: one violationMsg-shaped dict per Result of `objs`, from AuditStream's table

@@ -494,6 +494,79 @@ typedef struct {
 } gk_table_violations_out;
 int gk_table_violations(gk_engine* e, gk_table* t, uint64_t cursor, uint32_t max_entries, uint32_t flags, gk_table_violations_out** out);
 void gk_table_violations_free(gk_table_violations_out* o);
+/* What CHANGED in that answer since an earlier list-based audit cycle: the table counterpart of gk_resident_changes.  A list-based cycle
+ * makes a new table per cycle -- objects in whatever order the listing gives, appearing and disappearing, possibly under another policy
+ * set -- so the earlier answer is kept in a SNAPSHOT and the two are joined by object key.
+ * For a table with a collected evaluation let S(t) be the map {object -> (viol mask, err mask)} that a complete gk_table_violations
+ * stream of t returns, by that stream's exact rules: device bits of a review beyond the limits are never reported, the pairs the host
+ * evaluation of the same evaluation added are merged in, a review nobody answered has no entry and counts in beyond_limits.
+ * gk_table_snapshot keeps S(t) as it stands: on the device a flat copy of the violation and autoreject bitmaps of all plan groups (device
+ * to device) and the OR of their too_big words; on the host the sparse host-evaluated pairs, the constraint id of every mask bit, the
+ * exact object keys (group, version, kind, namespace, name; no hash stands in for a key) in key order, and the optional per-object
+ * `versions` -- opaque 64-bit values, e.g. derived from metadata.resourceVersion.  No rows, no text.  A snapshot never changes, survives
+ * gk_table_free of its table and any policy change (it carries its own ids), and any number of streams may be read against it.
+ * gk_table_changes streams what differs between S(then) and S(t).  Objects are joined by key; when a key occurs several times in a table
+ * its i-th occurrence in review order matches the i-th on the other side; a review with an empty key (rejected by HandleReview) matches
+ * nothing.  Bit r of EVERY mask of the output, was_* included, is constraint_ids[r] of the table now: a snapshot row moves to the row of
+ * the same constraint id, rows of constraints that are no longer loaded are dropped (the consumer drops what it holds for an id that is
+ * no longer listed), rows of new ids read as zero then.  A changed constraint set or another split into plan groups is therefore NOT a
+ * reset.  An object has an entry iff its masks now differ from its row-translated masks then (a side it is absent from counts as zero),
+ * or both sides gave `versions`, it is on both sides, its version differs and it has a result now (its messages may differ).  An object
+ * that is beyond the limits and unanswered NOW gets no entry whatever it had then and counts in beyond_limits: the consumer keeps what
+ * it holds (fail closed).  Unanswered THEN reads as zero then; was_beyond_limits is the snapshot's count.  entry_flags: GK_CHANGE_GONE --
+ * the object is not in the table now, reviews[i] = UINT32_MAX; GK_CHANGE_NEW -- it is not in the snapshot, was_reviews[i] = UINT32_MAX;
+ * GK_CHANGE_VERSION -- it matched and its version differs.  A consumer applies the entries in stream order, "state[key] := now".
+ * Order and pages: the entries of objects in the table now come first, ascending by review index, then the gone ones, ascending by the
+ * snapshot's review index.  A page is the longest run of whole 64-review words of ONE side whose entries fit in max_entries (below 64
+ * counts as 64; at least one word); no page inside a stream is empty.  cursor 0 begins a stream -- `then`, `versions` and `flags` are
+ * read there --, next_cursor continues it and is opaque; a later page must name the same `then`.  then == NULL: reset = 1 and the stream
+ * is the whole state, exactly gk_table_violations' entries with was_* = 0 and GK_CHANGE_NEW on every entry.
+ * The device lines the snapshot's bits up with the table's reviews and rows once per stream (the join itself is a merge of the two key
+ * orders on the host, O(n)), marks the differing reviews per bitmap word and compacts them into entries with four masks each; reviews
+ * the host evaluation answered on either side are compared on the host.
+ * GK_ERR_INVALID, never an answer from other bitmaps, as gk_table_violations: a table that was never evaluated, a stale table, policies
+ * changed since the table's evaluation, GK_EVAL_ASYNC launches still to be collected, a table set up as a shard, GK_CHANGES_RENDER
+ * without kept docs or text, a cursor from before any launch that wrote the table's result buffers ("... start again with cursor 0");
+ * and: a snapshot of another engine, a later page with another `then`.  gk_table_snapshot refuses the same table states.  With
+ * GK_CHANGES_RENDER, results_json[i] is byte for byte gk_table_violations' rendering for every entry with a result now, NULL otherwise. */
+#define GK_CHANGE_NEW 2u
+#define GK_CHANGE_VERSION 4u
+typedef struct gk_snapshot gk_snapshot;
+struct gk_snapshot_info {           /* (a struct tag: the call below has the same name) */
+  uint32_t n_reviews, n_constraints;
+  const uint32_t* constraint_ids;   /* [n_constraints], the bitmap-row order of the evaluation kept; valid while the snapshot lives */
+  uint64_t device_bytes, host_bytes;
+  uint64_t beyond_limits;
+};
+typedef struct {
+  uint32_t n_reviews, n_then;       /* reviews of the table / of the snapshot (0 without one) */
+  uint32_t n_constraints, mask_words;   /* of the table now; mask_words = ceil(n_constraints / 64) */
+  const uint32_t* constraint_ids;   /* [n_constraints], bitmap-row order of the table's evaluation: bit r of every mask */
+  uint32_t reset;                   /* 1: then == NULL, the stream is the whole state */
+  uint64_t total_entries;           /* entries of the WHOLE stream, on every page */
+  uint32_t n_entries;               /* on this page */
+  const uint32_t* reviews;          /* [n_entries] review index in the table; UINT32_MAX: gone */
+  const uint32_t* was_reviews;      /* [n_entries] review index in the snapshot; UINT32_MAX: new */
+  const char* const* keys;          /* [n_entries] JSON array ["group","version","kind","namespace","name"] */
+  const uint64_t* viol;             /* [n_entries][mask_words] violated constraints now */
+  const uint64_t* err;              /* [n_entries][mask_words] autoreject now */
+  const uint64_t* was_viol;         /* [n_entries][mask_words] ... in the snapshot, in the rows of the table now */
+  const uint64_t* was_err;          /* [n_entries][mask_words] */
+  const uint32_t* entry_flags;      /* [n_entries] GK_CHANGE_GONE | GK_CHANGE_NEW | GK_CHANGE_VERSION */
+  const char* const* results_json;  /* [n_entries] with GK_CHANGES_RENDER (NULL for an entry without results now); else NULL */
+  uint64_t beyond_limits;           /* as gk_table_violations_out, of the table now */
+  uint64_t was_beyond_limits;       /* ... of the snapshot */
+  uint64_t next_cursor;             /* 0: last page */
+  float device_ms;                  /* HIP-event time of this call's kernels */
+  float align_ms, index_ms, emit_ms;   /* diagnostic, no part of the contract above: device_ms by kernel (gk_tchg_align / _index / _emit) */
+} gk_table_changes_out;
+/* keep the answer of the table's most recent collected evaluation; the table may be freed afterwards */
+int gk_table_snapshot(gk_engine* e, gk_table* t, const uint64_t* versions /* [n_reviews] or NULL */, gk_snapshot** out);
+void gk_snapshot_free(gk_snapshot* s);
+int gk_snapshot_info(const gk_snapshot* s, struct gk_snapshot_info* out);
+int gk_table_changes(gk_engine* e, gk_table* t, const gk_snapshot* then /* or NULL */, const uint64_t* versions /* [n_reviews] or NULL */,
+                     uint64_t cursor, uint32_t max_entries, uint32_t flags, gk_table_changes_out** out);
+void gk_table_changes_free(gk_table_changes_out* o);
 /* results of one swept object, in gk_query's JSON; GK_ERR_NOT_FOUND when the object is unknown or its answer is stale */
 int gk_resident_review(gk_engine* e, const char* const* path, size_t npath, char** results_json);
 /* the same for a caller that matched itself (gk_query_ex2's arguments).  With GK_QUERY_PRE_MATCHED the sweep's bitmaps -- match AND
