@@ -17,6 +17,8 @@
 // kKernelBodyRw: the kernel body with the review-words hooks, made from kernel_body.inc at build time (embed_sources.py, the Makefile's
 // jit_body_rw.inc).  The two libraries include it in front of this header and define GK_HAVE_BODY_RW; a program that compiles this header
 // alone gets the plain text only and an exception where it asks for the variant.
+// kKernelBodyCold / kKernelBodyRwCold: the COLD-ARGUMENTS variants of the two (cold_args.hip spliced in by embed_sources.py, the Makefile's
+// jit_body_cold.inc), under the same rule with GK_HAVE_BODY_COLD.
 
 namespace gk {
 
@@ -117,6 +119,24 @@ inline std::string jit_res_macros() {
          flush + voids + "} while (0)\n";
 }
 
+// COLD ARGUMENTS (cold_args.hip): the text whose per-item tail and epilogue read the launch arguments only they use from the
+// kernel-argument segment.  Asked for wherever the review-words variant is eligible, with or without hoisted classes -- the plan-specialised
+// kernel of a table with row groups of 128 reviews and more and at least 8192 reviews (GK_JIT_COLD_ARGS_MIN=<n>: test aid) --, except for
+// shard passes and builds with the profiling aids, which keep their text.  GK_JIT_COLD_ARGS=0: off (the parent's text, same hash);
+// GK_JIT_COLD_ARGS=force (tuning / test aid): the variant for every text assemble_jit_source is asked for, whoever asks -- the GPU-less
+// build dumps it that way (tests/test_cold_args_text.py).
+inline bool cold_args_enabled() {
+  static const bool on = !(getenv("GK_JIT_COLD_ARGS") && std::string(getenv("GK_JIT_COLD_ARGS")) == "0");
+  return on;
+}
+inline uint32_t cold_args_min_reviews() {
+  static const uint32_t n = getenv("GK_JIT_COLD_ARGS_MIN") ? (uint32_t)atoll(getenv("GK_JIT_COLD_ARGS_MIN")) : 8192u;
+  return n;
+}
+inline bool cold_args_wanted(uint32_t rpt, uint32_t n_reviews, bool shard) {
+  return cold_args_enabled() && !shard && rpt >= 128u && n_reviews >= cold_args_min_reviews() && !getenv("GK_KERNEL_PROF") && !getenv("GK_DBG_PHASE");
+}
+
 // plan_hpp / vm_core_hpp / kernel_body: plan.hpp, vm_core.hpp and kernel_body.inc as text (build/jit_sources.inc)
 // rw_words: the global words of the plan's review-word classes (review_words.hpp) -- set and not empty: the text is the REVIEW-WORDS
 // variant (two more kernel parameters; the words of a review come from the binding's array instead of the hoisted classes' chunks);
@@ -124,7 +144,8 @@ inline std::string jit_res_macros() {
 // the GPU-less build dumps it that way and puts it through hiprtc (tests/test_review_words_text.py).
 inline std::string assemble_jit_source(const HostPlan& plan, uint32_t rpt, uint32_t rpp, const char* plan_hpp,
                                        const char* vm_core_hpp, const char* kernel_body, uint32_t list_cap = 0,
-                                       const std::vector<uint32_t>* rw_words = nullptr) {
+                                       const std::vector<uint32_t>* rw_words = nullptr, bool cold = false) {
+  if (const char* f = getenv("GK_JIT_COLD_ARGS"); f && std::string(f) == "force") cold = true;
   std::vector<uint32_t> rw_forced;
   if (const char* f = getenv("GK_JIT_REVIEW_WORDS"); !rw_words && f && std::string(f) == "force") {
     std::vector<std::vector<Pred>> classes;
@@ -211,6 +232,12 @@ inline std::string assemble_jit_source(const HostPlan& plan, uint32_t rpt, uint3
     while (fgets(buf, sizeof buf, f)) { line = buf; if (line.rfind("#include", 0) != 0 && line.rfind("#pragma once", 0) != 0) body += line; }
     fclose(f);
     src += body;
+  } else if (cold) {
+#ifdef GK_HAVE_BODY_COLD
+    src += rw ? kKernelBodyRwCold : kKernelBodyCold;
+#else
+    throw std::runtime_error("the cold-arguments kernel body is not part of this build");
+#endif
   } else if (rw) {
 #ifdef GK_HAVE_BODY_RW
     src += kKernelBodyRw;
