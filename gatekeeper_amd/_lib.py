@@ -39,6 +39,8 @@ GK_CHANGES_RESTART = 2
 GK_CHANGE_GONE = 1
 GK_CHANGE_NEW = 2
 GK_CHANGE_VERSION = 4
+GK_CHANGES_DEVICE_JOIN = 4
+GK_SNAPSHOT_DEVICE_KEYS = 1
 
 EXPORTS = [
     "gk_engine_create", "gk_engine_destroy", "gk_last_error", "gk_version", "gk_template_add", "gk_template_remove",
@@ -46,7 +48,7 @@ EXPORTS = [
     "gk_table_eval", "gk_eval_free", "gk_render", "gk_render_error", "gk_free", "gk_dump", "gk_table_review_words", "gk_table_topk", "gk_topk_free",
     "gk_table_totals", "gk_totals_free", "gk_table_get_stats", "gk_batcher_start", "gk_batcher_stop", "gk_query", "gk_query_ex", "gk_query_ex2",
     "gk_resident_sweep", "gk_sweep_free", "gk_resident_review", "gk_resident_review_ex", "gk_resident_audit", "gk_audit_free",
-    "gk_resident_violations", "gk_violations_free", "gk_resident_changes", "gk_changes_free", "gk_table_violations", "gk_table_violations_free", "gk_table_snapshot", "gk_snapshot_free", "gk_snapshot_info", "gk_table_changes", "gk_table_changes_free", "gk_table_verify", "gk_verify_free", "gk_resident_verify",
+    "gk_resident_violations", "gk_violations_free", "gk_resident_changes", "gk_changes_free", "gk_table_violations", "gk_table_violations_free", "gk_table_snapshot", "gk_snapshot_free", "gk_snapshot_info", "gk_table_changes", "gk_table_changes_free", "gk_table_snapshot_ex", "gk_table_join", "gk_table_join_free", "gk_table_changes_join", "gk_table_verify", "gk_verify_free", "gk_resident_verify",
     "gk_comm_unique_id", "gk_comm_init", "gk_comm_destroy", "gk_comm_info", "gk_table_sweep_sharded", "gk_shard_free",
     "gk_jit_quiesce", "gk_jit_cache_stats", "gk_jit_cache_dir", "gk_jit_cache_drop_memory", "gk_host_cpus", "gk_table_create_spool", "gk_spool_info_free", "gk_debug_set",
     # include/gksynth.h (bench / test plumbing)
@@ -143,6 +145,15 @@ class gk_table_changes_out(C.Structure):
                 ("entry_flags", C.POINTER(C.c_uint32)), ("results_json", C.POINTER(C.c_char_p)), ("beyond_limits", C.c_uint64),
                 ("was_beyond_limits", C.c_uint64), ("next_cursor", C.c_uint64), ("device_ms", C.c_float),
                 ("align_ms", C.c_float), ("index_ms", C.c_float), ("emit_ms", C.c_float)]
+
+
+class gk_join_stats(C.Structure):
+    _fields_ = [("n_now", C.c_uint32), ("n_then", C.c_uint32), ("capacity", C.c_uint32), ("host_resolved_now", C.c_uint32), ("host_resolved_then", C.c_uint32),
+                ("device", C.c_uint32), ("fallback", C.c_uint32), ("join_ms", C.c_float), ("pack_ms", C.c_float)]
+
+
+class gk_table_join_out(C.Structure):
+    _fields_ = [("n_now", C.c_uint32), ("n_then", C.c_uint32), ("then_of", C.POINTER(C.c_uint32)), ("now_of", C.POINTER(C.c_uint32)), ("stats", gk_join_stats)]
 
 
 class gk_table_violations_out(C.Structure):
@@ -313,6 +324,11 @@ def load(hostemu: bool | None = None):
     lib.gk_table_changes.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64), C.c_uint64, u32, u32, C.POINTER(C.POINTER(gk_table_changes_out))]
     lib.gk_table_changes_free.argtypes = [C.POINTER(gk_table_changes_out)]
     lib.gk_table_changes_free.restype = None
+    lib.gk_table_snapshot_ex.argtypes = [vp, vp, C.POINTER(C.c_uint64), u32, C.POINTER(vp)]
+    lib.gk_table_join.argtypes = [vp, vp, vp, u32, C.POINTER(C.POINTER(gk_table_join_out))]
+    lib.gk_table_join_free.argtypes = [C.POINTER(gk_table_join_out)]
+    lib.gk_table_join_free.restype = None
+    lib.gk_table_changes_join.argtypes = [vp, vp, C.POINTER(gk_join_stats)]
     lib.gk_table_verify.argtypes = [vp, vp, u32, u32, C.POINTER(C.POINTER(gk_verify_out))]
     lib.gk_verify_free.argtypes = [C.POINTER(gk_verify_out)]
     lib.gk_verify_free.restype = None

@@ -4,9 +4,11 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <string_view>
 #include <vector>
 
 #include "flatten.hpp"
+#include "key_join.hpp"
 #include "lower.hpp"
 #include "verify_merge.hpp"
 
@@ -164,6 +166,36 @@ void dev_tchg_entries(const std::vector<TviolSide>& sides, uint32_t n, const Dev
 // as dev_tviol_note / dev_tviol_forget, for the CPU stand-in of the entries above (the device does nothing here)
 void dev_tchg_note(const DevTable* t, const EvalOut& o);
 void dev_tchg_forget(const DevTable* t);
+// ---- the key join of a changes stream on the device (GK_CHANGES_DEVICE_JOIN, gk_table_join; key_join.hpp holds the pure part).
+// dev_keys_put: one side's packed key records and their offsets (kjoin_pack) on the device; the holder owns its memory (device pool) as
+// a DevSnap does and outlives whatever the keys were packed from.
+// dev_kjoin: delta_join's three arrays, bit for bit, from an exact hash join of the two sides' records -- gk_kjoin_build over the
+// snapshot's reviews, gk_kjoin_probe over the table's, gk_kjoin_finish over both, back to back on one stream; hashes are masked to
+// `hash_bits` bits (kjoin_mask).  What the kernels cannot pair without the occurrence rule -- every review whose key occurs more than
+// once on some side and is present in the snapshot -- comes back as flagged_now / flagged_then bit words and is settled by
+// kjoin_resolve on the host (key_now / key_then are asked for those reviews only); unmatched takes their bits from there.  It throws
+// KjoinFault when the kernels set their error word (a probe loop that ran out of slots, a record outside the arena): nothing of the
+// answer is used then.  *keep, when asked for, holds then_of as it stands on the device, the flagged reviews patched, for the
+// dev_tchg_align overload below (no second upload); the caller frees it (dev_join_free).  *ms: HIP-event time of the three kernels
+// (the CPU stand-in: 0).
+struct DevKeys;
+struct DevJoin;
+// (a side's key accessor: a plain function with its context -- it is called from sort comparators)
+struct KjKeyFn {
+  std::string_view (*fn)(const void* ctx, uint32_t review);
+  const void* ctx;
+  std::string_view operator()(uint32_t review) const { return fn(ctx, review); }
+};
+DevKeys* dev_keys_put(int device, const KjUnit* rec, size_t units, const uint32_t* off, uint32_t n);
+void dev_keys_free(DevKeys* k);
+uint64_t dev_keys_bytes(const DevKeys* k);
+void dev_kjoin(const DevKeys* now, const DevKeys* then, uint32_t hash_bits, const KjKeyFn& key_now, const KjKeyFn& key_then, std::vector<uint32_t>* then_of,
+               std::vector<uint32_t>* now_of, std::vector<uint64_t>* unmatched, std::vector<uint64_t>* flagged_now, std::vector<uint64_t>* flagged_then, KjoinStats* stats,
+               float* ms, DevJoin** keep = nullptr);
+void dev_join_free(DevJoin* j);
+// dev_tchg_align with then_of taken from a finished dev_kjoin (n = its now side's reviews)
+DevAligned* dev_tchg_align(int device, const DevSnap* s, uint32_t n, const DevJoin& then_of, const std::vector<uint32_t>& row_of, const std::vector<uint64_t>* moved,
+                           const std::vector<uint64_t>* only, float* ms);
 // the violation bitmap [nc][n_tiles] of the table's most recent evaluation (device -> host copy)
 void dev_last_viol(const DevTable* t, uint32_t nc, std::vector<uint64_t>* viol);
 // ---- the plan-specialised kernel checked against the bytecode kernel (gk_table_verify).

@@ -40,6 +40,7 @@
 using namespace gk;
 
 static std::atomic<int64_t> g_debug_verify_flip{-1};   // gk_debug_set("verify_flip", v): fault injection for gk_table_verify (gkgpu.h)
+static std::atomic<uint32_t> g_debug_kjoin_hash_bits{64};   // gk_debug_set("kjoin_hash_bits", b): the device key join masks its hashes to b bits (gkgpu.h)
 static std::atomic<bool> g_debug_keep_slot_index{false};   // gk_debug_set("keep_slot_index", 1): tables created from now on keep the host copy of their slot index (gk_table_review_words)
 static std::atomic<int> g_debug_group_max{0};   // gk_debug_set("group_max", n): plan groups of at most n constraints (0 = as many as fit)
 namespace {
@@ -499,7 +500,15 @@ struct gk_table {
     DeltaKnownMap known[2];
     std::vector<uint32_t> then_of;
     uint64_t beyond = 0;
+    bool joined = false;                    // the stream has a snapshot: `join` says how the two sides were joined (gk_table_changes_join)
+    KjoinStats join;
+    float join_ms = 0;
   } tc;
+  // the table's keys as packed records on the device (key_join.hpp), put there by the first device join and kept with the table;
+  // keys_unfit: they do not fit 32-bit offsets, every join of this table runs on the host
+  DevKeys* dkeys = nullptr;
+  bool keys_unfit = false;
+  std::mutex keys_mu;
   uint32_t n_reviews = 0;
   uint32_t rpt = GK_RPT_MIN;                // reviews per row group of this table
   uint64_t dict_gen = 0;                    // generation of the dictionary-predicate registry the rows were flattened under
@@ -1767,6 +1776,7 @@ void gk_table_free(gk_table* t) {
   if (!t) return;
   for (DevTable* v : t->tviews) dev_table_free(v);
   table_changes_drop(t);
+  dev_keys_free(t->dkeys);
   for (size_t g = t->sides.size(); g-- > 0;) {   // (views before the table: side 0 last)
     gk_table::Side& s = t->sides[g];
     if (s.vview) { dev_verify_forget(s.vview); dev_table_free(s.vview); }
@@ -3901,11 +3911,37 @@ struct gk_snapshot {
   uint64_t beyond = 0;
   std::string key_bytes;                  // the reviews' keys one after the other ...
   std::vector<std::pair<uint64_t, uint32_t>> key_span;   // ... (offset, length) per review
-  std::vector<uint32_t> order;            // the reviews in key order (table_key_order)
+  // the reviews in key order (table_key_order).  A snapshot taken with GK_SNAPSHOT_DEVICE_KEYS does not sort: key_order() builds the
+  // order when a host join first asks for it.  dkeys: the keys as packed records on the device (key_join.hpp), uploaded when the
+  // snapshot is taken with that flag, else by the first device join against it (device_keys()); keys_unfit: they do not fit.  Both
+  // are filled in once, under lazy_mu: a snapshot never changes otherwise, and any number of streams may read it.
+  mutable std::vector<uint32_t> order;
+  mutable DevKeys* dkeys = nullptr;
+  mutable bool keys_unfit = false;
+  mutable std::mutex lazy_mu;
   std::vector<uint64_t> versions;
   bool has_versions = false;
   std::string_view key(size_t i) const { return std::string_view(key_bytes.data() + key_span[i].first, key_span[i].second); }
-  ~gk_snapshot() { dev_snap_free(dev); }
+  const std::vector<uint32_t>& key_order() const {
+    std::lock_guard<std::mutex> l(lazy_mu);
+    if (order.size() != n_reviews) {
+      order.resize(n_reviews);
+      for (uint32_t i = 0; i < n_reviews; i++) order[i] = i;
+      std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
+    }
+    return order;
+  }
+  // nullptr: the keys do not fit 32-bit offsets in 16-byte units
+  const DevKeys* device_keys(int device) const {
+    std::lock_guard<std::mutex> l(lazy_mu);
+    if (!dkeys && !keys_unfit) {
+      KjPacked pk;
+      if (!kjoin_pack(n_reviews, [&](uint32_t i) { return key(i); }, &pk)) keys_unfit = true;
+      else dkeys = dev_keys_put(device, pk.rec.data(), pk.rec.size(), pk.off.data(), n_reviews);
+    }
+    return dkeys;
+  }
+  ~gk_snapshot() { dev_snap_free(dev); dev_keys_free(dkeys); }
 };
 
 namespace {
@@ -3955,10 +3991,94 @@ std::vector<uint32_t> narrow_slice(const std::vector<uint64_t>& prefix, uint32_t
 std::vector<uint64_t> word_slice(const std::vector<uint64_t>& words, uint32_t w0, uint32_t w1) {
   return words.empty() ? std::vector<uint64_t>() : std::vector<uint64_t>(words.begin() + w0, words.begin() + w1);
 }
+// The key join of the table with a snapshot (delta_join's three arrays).  on_device: the exact hash join of the two sides' packed keys
+// (dev_kjoin) -- the table's keys go up once and stay with the table, the snapshot's are its own; neither side is sorted.  When a side's
+// keys do not fit, or the kernels report an error, the host join answers and st->fallback says why.  Else: table_key_order + delta_join.
+// *keep (device join only): then_of on the device, for dev_tchg_align.
+void table_join(gk_engine* e, gk_table* t, const gk_snapshot* then, bool on_device, std::vector<uint32_t>* then_of, std::vector<uint32_t>* now_of,
+                std::vector<uint64_t>* unmatched, KjoinStats* st, float* ms, DevJoin** keep) {
+  *ms = 0;
+  if (keep) *keep = nullptr;
+  uint32_t fallback = 0;
+  float pack_ms = 0;
+  if (on_device) {
+    const DevKeys* dn = nullptr;
+    {
+      std::lock_guard<std::mutex> l(t->keys_mu);
+      if (!t->dkeys && !t->keys_unfit) {
+        const auto t0 = std::chrono::steady_clock::now();
+        KjPacked pk;
+        if (!kjoin_pack(t->n_reviews, [&](uint32_t i) { return t->obj_key(i); }, &pk)) t->keys_unfit = true;
+        else t->dkeys = dev_keys_put(e->opts.device, pk.rec.data(), pk.rec.size(), pk.off.data(), t->n_reviews);
+        pack_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      }
+      dn = t->dkeys;
+    }
+    const DevKeys* dt = dn ? then->device_keys(e->opts.device) : nullptr;
+    if (!dn || !dt) fallback = 1;
+    else {
+      try {
+        std::vector<uint64_t> flagged_now, flagged_then;
+        const KjKeyFn key_now{[](const void* c, uint32_t i) { return static_cast<const gk_table*>(c)->obj_key(i); }, t};
+        const KjKeyFn key_then{[](const void* c, uint32_t i) { return static_cast<const gk_snapshot*>(c)->key(i); }, then};
+        dev_kjoin(dn, dt, g_debug_kjoin_hash_bits.load(), key_now, key_then, then_of, now_of, unmatched, &flagged_now, &flagged_then, st, ms, keep);
+        st->pack_ms = pack_ms;
+        return;
+      } catch (const KjoinFault&) { fallback = 2; *ms = 0; }
+    }
+  }
+  table_key_order(t);
+  delta_join(t->order, [&](uint32_t i) { return t->obj_key(i); }, then->key_order(), [&](uint32_t i) { return then->key(i); }, then_of, now_of, unmatched);
+  *st = KjoinStats();
+  st->n_now = t->n_reviews; st->n_then = then->n_reviews; st->fallback = fallback; st->pack_ms = pack_ms;
+}
+void join_stats_out(const KjoinStats& st, float ms, struct gk_join_stats* out) {
+  memset(out, 0, sizeof *out);
+  out->n_now = st.n_now; out->n_then = st.n_then; out->capacity = st.capacity;
+  out->host_resolved_now = st.host_resolved_now; out->host_resolved_then = st.host_resolved_then;
+  out->device = st.device; out->fallback = st.fallback; out->join_ms = ms; out->pack_ms = st.pack_ms;
+}
+struct TableJoinHolder {
+  gk_table_join_out pub;   // first member
+  std::vector<uint32_t> then_of, now_of;
+};
 }  // namespace
 
-int gk_table_snapshot(gk_engine* e, gk_table* t, const uint64_t* versions, gk_snapshot** out) {
+int gk_table_join(gk_engine* e, gk_table* t, const gk_snapshot* then, uint32_t flags, gk_table_join_out** out) {
+  if (!e || !t || !then || !out) return fail(GK_ERR_INVALID, "NULL argument");
+  if (flags & ~GK_CHANGES_DEVICE_JOIN) return fail(GK_ERR_INVALID, "gk_table_join: unknown flags");
+  if (then->eng != e || t->eng != e) return fail(GK_ERR_INVALID, "gk_table_join: the snapshot belongs to another engine");
+  try {
+    std::unique_ptr<TableJoinHolder> h(new TableJoinHolder());
+    std::vector<uint64_t> unmatched;
+    KjoinStats st;
+    float ms = 0;
+    table_join(e, t, then, (flags & GK_CHANGES_DEVICE_JOIN) != 0, &h->then_of, &h->now_of, &unmatched, &st, &ms, nullptr);
+    memset(&h->pub, 0, sizeof h->pub);
+    h->pub.n_now = t->n_reviews; h->pub.n_then = then->n_reviews;
+    h->pub.then_of = h->then_of.data(); h->pub.now_of = h->now_of.data();
+    join_stats_out(st, ms, &h->pub.stats);
+    *out = &h.release()->pub;
+    return GK_OK;
+  } catch (const std::exception& ex) { return fail(GK_ERR_DEVICE, ex.what()); }
+}
+
+void gk_table_join_free(gk_table_join_out* o) { if (o) delete reinterpret_cast<TableJoinHolder*>(o); }
+
+int gk_table_changes_join(gk_engine* e, gk_table* t, struct gk_join_stats* out) {
   if (!e || !t || !out) return fail(GK_ERR_INVALID, "NULL argument");
+  if (t->tc.gen == 0 || t->tc.gen != t->ts_gen) return fail(GK_ERR_INVALID, "gk_table_changes_join: the table has no changes stream (gk_table_changes with cursor 0)");
+  KjoinStats none;   // (a stream without a snapshot joined nothing: all zero but the table's reviews)
+  none.n_now = t->tc.n[0];
+  join_stats_out(t->tc.joined ? t->tc.join : none, t->tc.joined ? t->tc.join_ms : 0.f, out);
+  return GK_OK;
+}
+
+int gk_table_snapshot(gk_engine* e, gk_table* t, const uint64_t* versions, gk_snapshot** out) { return gk_table_snapshot_ex(e, t, versions, 0, out); }
+
+int gk_table_snapshot_ex(gk_engine* e, gk_table* t, const uint64_t* versions, uint32_t flags, gk_snapshot** out) {
+  if (!e || !t || !out) return fail(GK_ERR_INVALID, "NULL argument");
+  if (flags & ~GK_SNAPSHOT_DEVICE_KEYS) return fail(GK_ERR_INVALID, "gk_table_snapshot_ex: unknown flags");
   try {
     if (const char* why = table_stale(e, t)) return fail(GK_ERR_INVALID, why);
     std::unique_ptr<gk_snapshot> s(new gk_snapshot());
@@ -3982,8 +4102,10 @@ int gk_table_snapshot(gk_engine* e, gk_table* t, const uint64_t* versions, gk_sn
       dev_tviol_index(sides, t->n_reviews, &cnt, nullptr, &dev_beyond, &ms);
       s->beyond = dev_beyond > s->host_done.size() ? dev_beyond - s->host_done.size() : 0;
     }
-    table_key_order(t);
-    s->order = t->order;
+    if (!(flags & GK_SNAPSHOT_DEVICE_KEYS)) {
+      table_key_order(t);
+      s->order = t->order;
+    }
     s->key_span.resize(t->n_reviews);
     size_t bytes = 0;
     for (size_t i = 0; i < t->n_reviews; i++) bytes += t->obj_key(i).size();
@@ -3994,6 +4116,7 @@ int gk_table_snapshot(gk_engine* e, gk_table* t, const uint64_t* versions, gk_sn
       s->key_bytes.append(k.data(), k.size());
     }
     if (versions) { s->versions.assign(versions, versions + t->n_reviews); s->has_versions = true; }
+    if (flags & GK_SNAPSHOT_DEVICE_KEYS) (void)s->device_keys(e->opts.device);   // (keys that do not fit: every join against it runs on the host)
     s->serial = ++g_snapshot_serial;
     *out = s.release();
     return GK_OK;
@@ -4007,7 +4130,8 @@ int gk_snapshot_info(const gk_snapshot* s, struct gk_snapshot_info* out) {
   memset(out, 0, sizeof *out);
   out->n_reviews = s->n_reviews; out->n_constraints = (uint32_t)s->ids.size();
   out->constraint_ids = s->ids.data();
-  out->device_bytes = dev_snap_bytes(s->dev);
+  std::lock_guard<std::mutex> l(s->lazy_mu);
+  out->device_bytes = dev_snap_bytes(s->dev) + dev_keys_bytes(s->dkeys);
   out->host_bytes = s->key_bytes.size() + s->key_span.size() * sizeof(s->key_span[0]) + (s->order.size() + s->ids.size() + s->host_done.size()) * 4u + s->versions.size() * 8u +
                     (s->host_viol.size() + s->host_err.size()) * 8u;
   out->beyond_limits = s->beyond;
@@ -4054,10 +4178,13 @@ int gk_table_changes(gk_engine* e, gk_table* t, const gk_snapshot* then, const u
         std::vector<uint32_t> row_of(nc, DELTA_NONE), now_row_of, now_of;
         std::vector<uint64_t> unmatched;
         C.then_of.assign(n_now, DELTA_NONE);
+        std::unique_ptr<DevJoin, void (*)(DevJoin*)> joined(nullptr, dev_join_free);   // then_of on the device, when the device joined
         if (then) {
           delta_row_map(h->ids, then->ids, &row_of, &now_row_of);
-          table_key_order(t);
-          delta_join(t->order, [&](uint32_t i) { return t->obj_key(i); }, then->order, [&](uint32_t i) { return then->key(i); }, &C.then_of, &now_of, &unmatched);
+          DevJoin* keep = nullptr;
+          table_join(e, t, then, (flags & GK_CHANGES_DEVICE_JOIN) != 0, &C.then_of, &now_of, &unmatched, &C.join, &C.join_ms, &keep);
+          joined.reset(keep);
+          C.joined = true;
           if (versions && then->has_versions) {
             C.moved.assign(words[0], 0);
             for (uint32_t r = 0; r < n_now; r++)
@@ -4070,7 +4197,8 @@ int gk_table_changes(gk_engine* e, gk_table* t, const gk_snapshot* then, const u
         }
         float ms = 0;
         // side 0: the table's reviews against what the snapshot holds of them
-        C.aligned[0] = dev_tchg_align(e->opts.device, then ? then->dev : nullptr, n_now, then ? &C.then_of : nullptr, row_of, C.moved.empty() ? nullptr : &C.moved, nullptr, &ms);
+        if (joined) C.aligned[0] = dev_tchg_align(e->opts.device, then->dev, n_now, *joined, row_of, C.moved.empty() ? nullptr : &C.moved, nullptr, &ms);
+        else C.aligned[0] = dev_tchg_align(e->opts.device, then ? then->dev : nullptr, n_now, then ? &C.then_of : nullptr, row_of, C.moved.empty() ? nullptr : &C.moved, nullptr, &ms);
         align_ms += ms;
         std::vector<uint32_t> cnt;
         std::vector<uint64_t> changed, big, entries;
@@ -4437,6 +4565,7 @@ int gk_debug_set(const char* key, int64_t value) {
   if (strcmp(key, "dict_facts") == 0) { g_debug_dict_facts.store(value != 0); return GK_OK; }
   if (strcmp(key, "group_max") == 0) { g_debug_group_max.store((int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20))); return GK_OK; }
   if (strcmp(key, "verify_flip") == 0) { g_debug_verify_flip.store(value < 0 ? -1 : value); return GK_OK; }
+  if (strcmp(key, "kjoin_hash_bits") == 0) { g_debug_kjoin_hash_bits.store(value < 0 || value > 64 ? 64u : (uint32_t)value); return GK_OK; }
   if (strcmp(key, "fold_match_labels") == 0) { g_test_fold_match_labels.store(value != 0); return GK_OK; }
   if (strcmp(key, "keep_slot_index") == 0) { g_debug_keep_slot_index.store(value != 0); return GK_OK; }
   return fail(GK_ERR_NOT_FOUND, std::string("gk_debug_set: unknown key ") + key);

@@ -437,27 +437,60 @@ class Table:
                     sets.append(got)
                 yield (int(r), sets[0], sets[1], pg["rows"][i]) if render else (int(r), sets[0], sets[1])
 
-    def snapshot(self, versions=None):
+    def snapshot(self, versions=None, device_keys=False):
         """Keep the answer of the most recent collected eval() (gk_table_snapshot): what a later table's change_pages() compares with.
         versions: one opaque 64-bit value per review (e.g. derived from metadata.resourceVersion), or None.  The table may be freed
-        afterwards; free the Snapshot when no stream needs it any more."""
+        afterwards; free the Snapshot when no stream needs it any more.  device_keys (GK_SNAPSHOT_DEVICE_KEYS): pack and upload the
+        object keys now, for later device joins, and do not sort them."""
         v = None
         if versions is not None:
             if len(versions) != self.n:
                 raise ValueError("versions: one value per review")
             v = (C.c_uint64 * max(1, self.n))(*[int(x) & 0xFFFFFFFFFFFFFFFF for x in versions])
         h = C.c_void_p()
-        self.engine._check(self.engine.lib.gk_table_snapshot(self.engine.handle, self.handle, v, C.byref(h)))
+        if device_keys:
+            self.engine._check(self.engine.lib.gk_table_snapshot_ex(self.engine.handle, self.handle, v, L.GK_SNAPSHOT_DEVICE_KEYS, C.byref(h)))
+        else:
+            self.engine._check(self.engine.lib.gk_table_snapshot(self.engine.handle, self.handle, v, C.byref(h)))
         return Snapshot(self.engine, h)
 
-    def change_pages(self, snapshot, page=4096, render=False, versions=None):
+    @staticmethod
+    def _join_stats(st):
+        return {f: (float(getattr(st, f)) if f.endswith("_ms") else int(getattr(st, f))) for f, _ in st._fields_}
+
+    def join(self, snapshot, device=False):
+        """gk_table_join: the objects of this table lined up with the snapshot's by key, without an evaluation in between.  Returns
+        (then_of [n] numpy, now_of [n_then] numpy, stats dict); 0xFFFFFFFF: new / gone.  device: the join runs on the device
+        (GK_CHANGES_DEVICE_JOIN), else on the host; both give the same arrays."""
+        if snapshot is None or not snapshot.handle:
+            raise ValueError("join: a live snapshot")
+        out = C.POINTER(L.gk_table_join_out)()
+        self.engine._check(self.engine.lib.gk_table_join(self.engine.handle, self.handle, snapshot.handle, L.GK_CHANGES_DEVICE_JOIN if device else 0, C.byref(out)))
+        try:
+            o = out.contents
+            then_of = np.ctypeslib.as_array(o.then_of, (int(o.n_now),)).copy() if o.n_now else np.zeros(0, np.uint32)
+            now_of = np.ctypeslib.as_array(o.now_of, (int(o.n_then),)).copy() if o.n_then else np.zeros(0, np.uint32)
+            return then_of, now_of, self._join_stats(o.stats)
+        finally:
+            self.engine.lib.gk_table_join_free(out)
+
+    def changes_join(self):
+        """gk_table_changes_join: how the current changes stream joined the two cycles, as a dict (device, fallback, capacity,
+        host_resolved_now / _then, join_ms, ...); all zero but n_now for a stream without a snapshot."""
+        st = L.gk_join_stats()
+        self.engine._check(self.engine.lib.gk_table_changes_join(self.engine.handle, self.handle, C.byref(st)))
+        return self._join_stats(st)
+
+    def change_pages(self, snapshot, page=4096, render=False, versions=None, device_join=False):
         """gk_table_changes page by page: what differs between `snapshot` (None: nothing, the stream is the whole state) and the most
         recent collected eval() of this table.  Yields dicts with `ids` (constraint id of every mask bit, this table's), `reset`,
         `reviews` / `was_reviews` ([n], 0xFFFFFFFF: gone / new), `keys` (per entry the (group, version, kind, namespace, name) tuple),
         `viol` / `err` / `was_viol` / `was_err` ([n][mask_words] numpy), `flags` ([n] GK_CHANGE_*), `rows` (with `render`: gk_query's
         rows for an entry with results now, else None), `total_entries`, `beyond_limits`, `was_beyond_limits`, `device_ms`,
-        `next_cursor`.  Frees each page."""
+        `next_cursor`.  Frees each page.  device_join (GK_CHANGES_DEVICE_JOIN): the two cycles' keys are joined on the device; the
+        stream is the same."""
         lib, cursor = self.engine.lib, 0
+        flags = (L.GK_CHANGES_RENDER if render else 0) | (L.GK_CHANGES_DEVICE_JOIN if device_join else 0)
         v = None
         if versions is not None:
             if len(versions) != self.n:
@@ -471,7 +504,7 @@ class Table:
             return np.ctypeslib.as_array(ptr, (n * mw,)).reshape(n, mw).copy() if n * mw else np.zeros((n, mw), np.uint64)
         while True:
             out = C.POINTER(L.gk_table_changes_out)()
-            self.engine._check(lib.gk_table_changes(self.engine.handle, self.handle, then, v, cursor, int(page), L.GK_CHANGES_RENDER if render else 0, C.byref(out)))
+            self.engine._check(lib.gk_table_changes(self.engine.handle, self.handle, then, v, cursor, int(page), flags, C.byref(out)))
             try:
                 o = out.contents
                 n, mw = int(o.n_entries), int(o.mask_words)
@@ -492,11 +525,11 @@ class Table:
             if not cursor:
                 return
 
-    def changes(self, snapshot, page=4096, render=False, versions=None):
+    def changes(self, snapshot, page=4096, render=False, versions=None, device_join=False):
         """change_pages() entry by entry: yields (key tuple, {"viol", "err", "was_viol", "was_err": [constraint ids]}, flags, rows,
         review, was_review) in stream order -- apply them in this order, state[key] := now.  self.beyond_limits /
         self.was_beyond_limits / self.changes_reset are set from the pages."""
-        for pg in self.change_pages(snapshot, page, render, versions):
+        for pg in self.change_pages(snapshot, page, render, versions, device_join):
             self.beyond_limits, self.was_beyond_limits, self.changes_reset = pg["beyond_limits"], pg["was_beyond_limits"], pg["reset"]
             ids = pg["ids"]
             for i, key in enumerate(pg["keys"]):
@@ -1247,8 +1280,8 @@ class AuditCycles:
     one downloading evaluation, gk_table_changes against the previous cycle's snapshot.  The new snapshot replaces the old one only when
     run()'s generator has been read to its end; close() frees it."""
 
-    def __init__(self, client, page=4096):
-        self.client, self.page, self.snapshot = client, page, None
+    def __init__(self, client, page=4096, device_join=False):
+        self.client, self.page, self.snapshot, self.device_join = client, page, None, device_join
 
     def run(self, objs, namespaces=None, versions=None):
         """Yields (key tuple (group, version, kind, namespace, name), appeared [Result], resolved [(constraint kind, name)], flags) per
@@ -1278,8 +1311,8 @@ class AuditCycles:
             for k in ev.too_big_reviews():
                 yield idx[k], ReviewFailure(idx[k], str(LimitError("review %d" % idx[k])), LimitError("review %d" % idx[k]))
             del ev
-            new = table.snapshot(vers)
-            for key, sets, flags, rows, _r, _p in table.changes(self.snapshot, self.page, render=True, versions=vers):
+            new = table.snapshot(vers, device_keys=self.device_join)
+            for key, sets, flags, rows, _r, _p in table.changes(self.snapshot, self.page, render=True, versions=vers, device_join=self.device_join):
                 res = []
                 for v in sorted((v for v in rows or () if v.get("autoreject")), key=lambda v: v["constraint"]):
                     if v["constraint"] in info:
@@ -1561,10 +1594,11 @@ class Client:
             if res:
                 yield i, res
 
-    def AuditCycles(self, page=4096):
+    def AuditCycles(self, page=4096, device_join=False):
         """The list-based audit for a caller that keeps the previous cycle's results: an AuditCycles whose run(objs) does one cycle and
-        yields only what changed since the cycle before (gk_table_changes against that cycle's snapshot)."""
-        return AuditCycles(self, page)
+        yields only what changed since the cycle before (gk_table_changes against that cycle's snapshot).  device_join: the two
+        cycles' object keys are joined on the device (GK_CHANGES_DEVICE_JOIN; snapshots keep their keys there)."""
+        return AuditCycles(self, page, device_join)
 
     def AuditMessages(self, objs, timestamp, namespaces=None, page=4096, msg_size=256):
         """AuditViolationMessages for the list-based audit: one violationMsg-shaped dict per Result of `objs`, from AuditStream's table

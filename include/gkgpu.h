@@ -535,7 +535,7 @@ typedef struct gk_snapshot gk_snapshot;
 struct gk_snapshot_info {           /* (a struct tag: the call below has the same name) */
   uint32_t n_reviews, n_constraints;
   const uint32_t* constraint_ids;   /* [n_constraints], the bitmap-row order of the evaluation kept; valid while the snapshot lives */
-  uint64_t device_bytes, host_bytes;
+  uint64_t device_bytes, host_bytes;   /* device_bytes includes the snapshot's device keys (GK_SNAPSHOT_DEVICE_KEYS, or uploaded by a later device join) when present */
   uint64_t beyond_limits;
 };
 typedef struct {
@@ -567,6 +567,42 @@ int gk_snapshot_info(const gk_snapshot* s, struct gk_snapshot_info* out);
 int gk_table_changes(gk_engine* e, gk_table* t, const gk_snapshot* then /* or NULL */, const uint64_t* versions /* [n_reviews] or NULL */,
                      uint64_t cursor, uint32_t max_entries, uint32_t flags, gk_table_changes_out** out);
 void gk_table_changes_free(gk_table_changes_out* o);
+/* The key join of the two cycles on the device, opt-in; the answer of every call above is the same with and without it.
+ * GK_CHANGES_DEVICE_JOIN, read at cursor 0 of gk_table_changes like the other stream flags: the table's keys are packed into records
+ * ([u32 length][bytes], 16-byte aligned) and uploaded once per table (kept with it, freed with it), the snapshot's device keys are used
+ * -- uploaded once, at the first such stream, when the snapshot was taken without them --, and three kernels build an exact hash table
+ * over the snapshot's keys, probe it with the table's and pair the objects: the table is keyed by the exact key bytes, a hash chooses a
+ * slot and never stands in for a key.  Objects whose key occurs more than once on a side and is present in the snapshot are paired by
+ * the host under the occurrence rule (host_resolved_*).  Neither table is sorted by key on this path.  It falls back to the host join,
+ * and says so, when a side's packed keys do not fit 32-bit offsets in 16-byte units (fallback 1) or the kernels report an error
+ * (fallback 2).  With then == NULL there is no join.
+ * gk_table_snapshot_ex with GK_SNAPSHOT_DEVICE_KEYS packs and uploads the snapshot's keys when it is taken and does not sort them (the
+ * key order a host join needs is built when one first asks for it); flags 0 is gk_table_snapshot.
+ * gk_table_join is the join on its own -- it needs the table's keys only, no evaluation: what a consumer uses to carry its own
+ * per-object state from one listing to the next.  flags: 0 the host join, GK_CHANGES_DEVICE_JOIN the device join.
+ * gk_table_changes_join: the join of the table's current changes stream (a stream without a snapshot joined nothing: all zero but
+ * n_now); GK_ERR_INVALID without a stream. */
+#define GK_CHANGES_DEVICE_JOIN 4u
+#define GK_SNAPSHOT_DEVICE_KEYS 1u
+struct gk_join_stats {
+  uint32_t n_now, n_then;           /* reviews of the table / of the snapshot */
+  uint32_t capacity;                /* slots of the device's table: the power of two >= 2 n_then; 0: the host join */
+  uint32_t host_resolved_now, host_resolved_then;   /* objects the host paired under the occurrence rule */
+  uint32_t device;                  /* 1: the device join ran, 0: the host join */
+  uint32_t fallback;                /* the device join was asked for and did not run: 1 a side's keys do not fit, 2 the kernels' error word; else 0 */
+  float join_ms;                    /* HIP-event time of the join's kernels (0: the host join) */
+  float pack_ms;                    /* diagnostic: host time to pack and upload the table's keys, when this call did */
+};
+typedef struct {
+  uint32_t n_now, n_then;
+  const uint32_t* then_of;          /* [n_now] the snapshot's review the table's review continues; UINT32_MAX: new */
+  const uint32_t* now_of;           /* [n_then] the inverse; UINT32_MAX: gone */
+  struct gk_join_stats stats;
+} gk_table_join_out;
+int gk_table_snapshot_ex(gk_engine* e, gk_table* t, const uint64_t* versions /* [n_reviews] or NULL */, uint32_t flags, gk_snapshot** out);
+int gk_table_join(gk_engine* e, gk_table* t, const gk_snapshot* then, uint32_t flags, gk_table_join_out** out);
+void gk_table_join_free(gk_table_join_out* o);
+int gk_table_changes_join(gk_engine* e, gk_table* t, struct gk_join_stats* out);
 /* results of one swept object, in gk_query's JSON; GK_ERR_NOT_FOUND when the object is unknown or its answer is stale */
 int gk_resident_review(gk_engine* e, const char* const* path, size_t npath, char** results_json);
 /* the same for a caller that matched itself (gk_query_ex2's arguments).  With GK_QUERY_PRE_MATCHED the sweep's bitmaps -- match AND
@@ -705,7 +741,9 @@ void gk_jit_cache_drop_memory(void);
  * keep a row per leaf instead of sharing the review facts row, for the policies loaded while it is 0); "verify_flip" (fault injection for
  * gk_table_verify / gk_resident_verify: -1 = off, else kind << 56 | whole_word << 55 | row << 32 | review with row in the merged
  * constraint_ids order and, for the resident set, review counted over the chunks -- the verifications that follow toggle that bit, with
- * whole_word all 64 bits of the word that holds it, on the bytecode side before they compare).  GK_ERR_NOT_FOUND for an unknown key. */
+ * whole_word all 64 bits of the word that holds it, on the bytecode side before they compare); "kjoin_hash_bits" (test aid for the device
+ * key join: the joins that follow mask their hashes to the low b bits, default 64 = all of it; 0 gives every key one home slot and one
+ * tag -- the answers do not depend on it).  GK_ERR_NOT_FOUND for an unknown key. */
 int gk_debug_set(const char* key, int64_t value);
 
 /* Debug: the compiled plan as text (Driver.Dump, pkg/drivers/k8scel/driver.go:253). */

@@ -15,6 +15,12 @@ joined by object on the host -- between two list-based audit cycles (profiles/ta
                                                                 the object's position in the first listing (numpy: sort + searchsorted + compare;
                                                                 an integer stands in for the key, which favours (b)).
                                                             Both are checked to name the same changed objects before anything is timed.
+                                                            --device-join adds, in the same process and on the same tables:
+                                                            (c) gk_table_changes with GK_CHANGES_DEVICE_JOIN against a snapshot taken with
+                                                                GK_SNAPSHOT_DEVICE_KEYS, checked to give (a)'s entries one by one; the first such
+                                                                call packs and uploads the table's keys (pack_ms), the repeats find them there;
+                                                            and, once, on the freshly built first table: gk_table_snapshot_ex with device keys
+                                                            (no sort) against gk_table_snapshot (the key sort, table_key_order).
 
 Workload: the configs[2] policy set.  Every wall time is a host clock around C calls that end in a stream synchronise; device_ms is the
 HIP-event time of a call's kernels.  Reads nothing outside the tree."""
@@ -111,14 +117,14 @@ def step_pair(args):
         cat = lambda xs, empty: np.concatenate(xs) if xs else empty   # noqa: E731
         return time.perf_counter() - t0, cat(revs, np.zeros(0, np.uint32)), cat(vs, np.zeros((0, mw), np.uint64)), cat(es, np.zeros((0, mw), np.uint64))
 
-    def changes(snap):
+    def changes(snap, call_flags=0):
         """the whole gk_table_changes stream -> (seconds per call, device_ms per call, changed first-listing positions or -1, gone, new)"""
         times, dev, cursor, who, flags, revs = [], [], 0, [], [], []
         by_kernel = np.zeros(3)
         while True:
             out = C.POINTER(L.gk_table_changes_out)()
             t0 = time.perf_counter()
-            rc = eng.lib.gk_table_changes(eng.handle, now.handle, snap.handle, None, cursor, 65536, 0, C.byref(out))
+            rc = eng.lib.gk_table_changes(eng.handle, now.handle, snap.handle, None, cursor, 65536, call_flags, C.byref(out))
             times.append(time.perf_counter() - t0)
             eng._check(rc)
             o = out.contents
@@ -161,8 +167,20 @@ def step_pair(args):
         return time.perf_counter() - t0, np.sort(changed)
 
     evaluate(then, 0)
+    snap_keys = None
+    if args.device_join:   # on the fresh table, the one without a sort first: gk_table_snapshot sorts the table's keys once and the table keeps the order
+        t0 = time.perf_counter()
+        snap_keys = then.snapshot(device_keys=True)
+        t_keys = time.perf_counter() - t0
+    t0 = time.perf_counter()
     snap = then.snapshot()
+    t_plain = time.perf_counter() - t0
     info = snap.info()
+    if snap_keys:
+        ik = snap_keys.info()
+        print("on the freshly built table: gk_table_snapshot_ex(GK_SNAPSHOT_DEVICE_KEYS) %.1f ms (no sort; %d B on the device, %d B on the host) | gk_table_snapshot %.1f ms "
+              "(table_key_order's sort; %d B on the device, %d B on the host)" % (t_keys * 1e3, ik["device_bytes"], ik["host_bytes"], t_plain * 1e3, info["device_bytes"], info["host_bytes"]),
+              flush=True)
     _, *kept = violations(then)
     then.free()                                                      # cycle 1's table is gone, as in a real audit; its answer is the snapshot / the kept stream
     evaluate(now, 0)
@@ -179,8 +197,23 @@ def step_pair(args):
           % (len(who), len(who) - n_gone - n_new, n_gone, n_new, len(in_a), len(in_b), same), flush=True)
     if not same or (args.keep_keys and (n_gone or n_new)):
         sys.exit(2)
+    c_all, c_first, c_later, c_join, c_stats = [], [], [], [], None
+    if snap_keys:   # (c) names what (a) names, entry by entry; this first call is the one that packs and uploads the table's keys
+        evaluate(now, L.GK_EVAL_NO_DOWNLOAD)
+        times, _, who_c, flags_c, _ = changes(snap_keys, L.GK_CHANGES_DEVICE_JOIN)
+        first_stats = now.changes_join()
+        if not (np.array_equal(who_c, who) and np.array_equal(flags_c, flags)) or first_stats["device"] != 1:
+            print("the device-join stream differs from the host-join stream, or the device did not join: %r" % (first_stats,), flush=True)
+            sys.exit(3)
+        print("(c) first device-join call on this table: cursor-0 call %.3f ms, of which key pack + upload of the now side %.3f ms; join kernels %.3f ms"
+              % (times[0] * 1e3, first_stats["pack_ms"], first_stats["join_ms"]), flush=True)
     a_all, a_first, a_later, a_dev, a_kern, b_all, b_stream, b_join = [], [], [], [], [], [], [], []
     for _ in range(args.repeat):
+        if snap_keys:
+            evaluate(now, L.GK_EVAL_NO_DOWNLOAD)
+            times, _, _, _, _ = changes(snap_keys, L.GK_CHANGES_DEVICE_JOIN)
+            c_stats = now.changes_join()
+            c_all.append(sum(times)); c_first.append(times[0]); c_later += times[1:]; c_join.append(c_stats["join_ms"] / 1e3)
         evaluate(now, L.GK_EVAL_NO_DOWNLOAD)                         # a new evaluation: the stream's state is built again at cursor 0
         times, dev, _, _, kern = changes(snap)
         a_all.append(sum(times)); a_first.append(times[0]); a_later += times[1:]; a_dev.append(dev); a_kern.append(kern)
@@ -196,13 +229,21 @@ def step_pair(args):
     kern = sorted(a_kern, key=sum)[len(a_kern) // 2]
     print("device time per kernel over the median changes stream, all its calls and both sides: gk_tchg_align %.3f ms | gk_tchg_index %.3f ms | gk_tchg_emit %.3f ms"
           % tuple(kern), flush=True)
+    if snap_keys:
+        print("(min / median / max) (c) gk_table_changes with the device join, keys already on the device, whole stream %s [cursor-0 call %s | later pages %s]"
+              % (stats(c_all), stats(c_first), stats(c_later) if c_later else "-"))
+        print("(c) cursor-0 + pack: %.3f ms = the median cursor-0 call of the repeats %.3f ms + the first call's key pack + upload %.3f ms (a sum of two measured figures: what "
+              "a cycle that builds a new table pays)" % (sorted(c_first)[len(c_first) // 2] * 1e3 + first_stats["pack_ms"], sorted(c_first)[len(c_first) // 2] * 1e3, first_stats["pack_ms"]))
+        print("(c) join kernels (HIP events) %s; capacity %d; host_resolved_now %d, host_resolved_then %d; fallback %d"
+              % (stats(c_join), c_stats["capacity"], c_stats["host_resolved_now"], c_stats["host_resolved_then"], c_stats["fallback"]), flush=True)
+        snap_keys.free()
     snap.free()
     now.free()
 
 
 def step_all(args):
     os.makedirs(args.out, exist_ok=True)
-    me = [sys.executable, os.path.abspath(__file__), "pair", "--objects", str(args.objects), "--repeat", str(args.repeat)]
+    me = [sys.executable, os.path.abspath(__file__), "pair", "--objects", str(args.objects), "--repeat", str(args.repeat)] + (["--device-join"] if args.device_join else [])
     steps = [(churn, shuffle, False) for churn in (0, 1, 100) for shuffle in (False, True)] + [(1, False, True), (1, True, True)]   # (fewer than 1 % of the objects keep their key under the other seed)
     for churn, shuffle, keep in steps:   # a fresh child per step, each under its own limit; a step that fails or runs out ends the run
         name = "churn%d_%s%s" % (churn, "shuffled" if shuffle else "same", "_keys_kept" if keep else "")
@@ -225,5 +266,6 @@ if __name__ == "__main__":
     ap.add_argument("--limit", type=int, default=240)
     ap.add_argument("--out", default="table_changes_out")
     ap.add_argument("--hostemu", action="store_true")
+    ap.add_argument("--device-join", action="store_true")
     a = ap.parse_args()
     {"all": step_all, "pair": step_pair}[a.step](a)
